@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: env-steps/s of Isaac-Velocity-Flat-H12_12dof-v0 random-action rollouts, 4096 envs per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 One step = one ManagerBasedRLEnv.step of every env on the GPU (4 physics steps of one implicit
@@ -17,12 +17,15 @@ time.  N = 1 is config C2 (no collective; --rollout on records on one GPU).
 
 Steady state: episode_length_buf is randomised first (rsl_rl's init_at_random_ep_len) and a fixed
 burn-in (--burn-in, untimed, on top of --warmup) lets falls and time-outs reach their steady rate, so
-any --steps window sees representative resets.  After the timed window the workspace snapshot taken
-before it is restored and the SAME window is replayed (bit-identical, checked) to count its resets
-and to time each kernel with HIP events bound to the dispatches (the interval rocprofv3 reports).
+any --steps window sees representative resets.
 
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel) and
-`cpu_baseline` (the CPU oracle on host cores, bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields;
+--dump-outputs DIR also writes what the last timed step returned (DIR/<name>.npy, float32), the same arrays
+from run to run for the same arguments.  --full adds everything else: after the timed window the workspace
+snapshot taken before it is restored and the SAME window is replayed (bit-identical, checked) to count its
+resets and to time each kernel with HIP events bound to the dispatches (the interval rocprofv3 reports), the
+C4 all-gather / decode split is measured in a pass of its own, and the line gains `roofline` (dominant kernel)
+and `cpu_baseline` (the CPU oracle on host cores, bounded sample).
 """
 from __future__ import annotations
 
@@ -48,6 +51,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--warmup", type=int, default=50)
+    p.add_argument("--full", action="store_true",
+                   help="also replay the timed window (reset count, bit-exactness, per-kernel HIP-event times and the "
+                        "roofline), measure the C4 all-gather / decode split and run the CPU baseline; off: the timed "
+                        "window and the contract fields only")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps rank 0 writes what the last timed step returned (policy observations, "
+                        "rewards, terminated / time-out flags) as DIR/<name>.npy, float32 (a fixed seeded sample of the "
+                        "envs if they exceed 64 MB)")
     p.add_argument("--burn-in", type=int, default=300,
                    help="untimed steps after randomising episode_length_buf, before --warmup (steady state)")
     p.add_argument("--envs", type=int, default=None, help="envs per GPU (the metric is quoted at 4096; C5 at 8192)")
@@ -94,6 +105,8 @@ def parse():
     p.add_argument("--dump-rollout", type=str, default=None,
                    help="test hook: rank 0 saves the decoded rows and the gathered records of the timed window (.npz)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
     if args.rollout == "on" and args.task not in ROLLOUT_TASKS:
         p.error(f"--rollout on: the compact rollout records rebuild history rows of the flat / rsl layouts only "
                 f"(--task {args.task} has {'no history' if args.task in ('rough', 'c5') else 'CaT dones'})")
@@ -218,6 +231,29 @@ def cpu_baseline(seconds: float):
             "single_env_sim2sim": mujoco,
             "sample": f"oracle/h12_oracle.c (fp64, OpenMP) on {n} envs x {steps} env steps "
                       f"({dt:.1f} s) of the same random-action Flat-H12 workload, {threads} host threads"}
+
+
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, arrays: dict):
+    """Write the last timed step's outputs (name -> (num_envs, ...) device tensor) as path/<name>.npy in float32: every
+    env while the arrays fit DUMP_BUDGET_BYTES together, else the same seeded sample of envs for each (their ids in
+    env_ids.npy)."""
+    import numpy as np
+
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().to("cpu").float().numpy() for k, v in arrays.items()}
+    n = next(iter(host.values())).shape[0]
+    per_env = sum(a.nbytes // n for a in host.values()) + 8  # + the env id
+    keep = DUMP_BUDGET_BYTES // per_env
+    if keep < n:
+        ids = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {k: a[ids] for k, a in host.items()}
+        host["env_ids"] = ids.astype(np.float64)
+    for k, a in host.items():
+        np.save(out / f"{k}.npy", np.ascontiguousarray(a))
 
 
 def train_mode(args, world, rank, dev, torch, dist):
@@ -381,7 +417,8 @@ def main():
                     rec.actions[s0 + k:s1].copy_(actions[:span - k])
             return f
 
-    snap = env.snapshot()  # replayed below (reset count + kernel timing of the same window); copied before the barrier
+    # --full: replayed below (reset count + kernel timing of the same window); copied before the barrier
+    snap = env.snapshot() if args.full else None
     barrier()
     # the env-stream span of the rollout path (C4 split); no event records in the plain timed window (each costs
     # host time, which a 20-step window does not amortise)
@@ -391,11 +428,11 @@ def main():
         ev_c[0].record()
     for i in range(K):
         if rg is None:
-            env.step(actions[(B + W + i) % pool])
+            last = env.step(actions[(B + W + i) % pool])
             continue
         rg.before_step()
         tc = rec.t
-        env.step(actions[(pool_off + i) % pool])
+        last = env.step(actions[(pool_off + i) % pool])
         rg.after_step(tc, put_actions(pool_off + i + 1))
     if rg is not None and K > 0:
         rg.flush(rec.t, put_actions(pool_off + K))
@@ -411,6 +448,12 @@ def main():
 
         D.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step (the tensors are the env's own buffers, or views
+        # of the rollout record: copied out before anything else steps the env)
+        obs, rew, term, trunc, _ = last
+        dump_outputs(args.dump_outputs, {"obs_policy": obs["policy"], "reward": rew, "terminated": term,
+                                         "time_outs": trunc})
     c4 = None
     if rg is not None and args.dump_rollout and rank == 0:
         import numpy as np
@@ -423,8 +466,8 @@ def main():
         np.savez(args.dump_rollout, obs=rg.obs[:te].cpu().numpy(), gathered=rg.records(0).cpu().numpy(),
                  tail=rg.tail.cpu().numpy(), off=np.array(rec.off), step_bytes=rec.step_bytes, T=te, G=rg.G,
                  n=n, world=world, burn_in=B, warmup=W, steps=K, pool=pool)
-    final_obs = env.get_observations()["policy"].clone()
-    if rg is not None and not args.profile_only:
+    final_obs = env.get_observations()["policy"].clone() if args.full else None
+    if rg is not None and args.full and not args.profile_only:
         # the split pass (untimed, after the window): two more rollouts with an event pair around every chunk's
         # gather and decode on the comm stream
         chunks_timed = rg.seq
@@ -465,6 +508,54 @@ def main():
             print(json.dumps({"profile_only": True, "ms_per_step": 1e3 * dt / K}))
         return
 
+    value = world * n * K / dt
+    metric, workload = METRIC, "Isaac-Velocity-Flat-H12_12dof-v0 random-action rollout, 4096 envs per MI355X"
+    if args.task in ("rsl", "cat"):
+        tid = {"rsl": "Rsl-H12_12dof", "cat": "CaT-Flat-H12_12dof"}[args.task]
+        metric = f"env-steps/sec at {n} envs, Velocity-{tid}"
+        workload = f"Isaac-Velocity-{tid}-v0 random-action rollout, {n} envs per MI355X"
+    elif args.task != "flat":
+        metric = f"env-steps/sec at {n} envs, Velocity-Rough-H12_12dof" + (" + friction/mass randomisation (C5)"
+                                                                           if args.task == "c5" else "")
+        workload = f"Isaac-Velocity-Rough-H12_12dof-v0 random-action rollout, {n} envs per MI355X" + (
+            ", CaT startup randomisation (BASELINE C5)" if args.task == "c5" else "")
+    line = {
+        "metric": metric,
+        "value": value,
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": 1e3 * dt / K,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic: N(0,1) random actions, reset distribution of the Flat task (seeded)",
+        "config": {
+            "workload": workload,
+            "envs_per_gpu": n,
+            "global_envs": n * world,
+            "decimation": cfg.decimation,
+            "physics_dt": cfg.sim.dt,
+            "inner_steps": cfg.sim.inner_steps,
+            "implicit_penalty": bool(cfg.sim.implicit_penalty),
+            "parallelism": f"env-shard x{world}" + (f" + RCCL all-gather of the rollout every {rg.G} steps"
+                                                     if rg is not None and world > 1 else ""),
+        },
+        "burn_in": B,
+    }
+    if not args.full:  # the plain run: the timed window and its line only
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if rg is not None:
+            env.unbind_rollout()
+        env.close()
+        if world > 1 or args.force_collective:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # replay of the timed window from the snapshot: count its resets and time each launch with HIP
     # events bound to the dispatches (kernel begin / end, as rocprofv3 reports them); the replay must
     # reproduce the timed window bit for bit
@@ -490,7 +581,6 @@ def main():
     obs_bytes_env, _ = env.kernel_cost(1)
     step_bytes_env, _ = env.step_cost()
 
-    value = world * n * K / dt
     if rank == 0:
         achieved = bytes_env * n / (kern_ms_avg * 1e-3) / 1e9
         pmc, pmc_src = load_pmc(args.pmc_file)
@@ -535,43 +625,10 @@ def main():
                 issue.update(pmc_valu_insts_per_wave_all_roles=sq["SQ_INSTS_VALU"] / sq["SQ_WAVES"],
                              waves=sq["SQ_WAVES"], simds_in_use_frac=sq["SQ_WAVES"] / N_SIMD,
                              wait_frac=sq.get("SQ_WAIT_ANY", 0.0) / sq.get("SQ_WAVE_CYCLES", 1.0), pmc_source=pmc_src)
-        metric, workload = METRIC, "Isaac-Velocity-Flat-H12_12dof-v0 random-action rollout, 4096 envs per MI355X"
-        if args.task in ("rsl", "cat"):
-            tid = {"rsl": "Rsl-H12_12dof", "cat": "CaT-Flat-H12_12dof"}[args.task]
-            metric = f"env-steps/sec at {n} envs, Velocity-{tid}"
-            workload = f"Isaac-Velocity-{tid}-v0 random-action rollout, {n} envs per MI355X"
-        elif args.task != "flat":
-            metric = f"env-steps/sec at {n} envs, Velocity-Rough-H12_12dof" + (" + friction/mass randomisation (C5)"
-                                                                               if args.task == "c5" else "")
-            workload = f"Isaac-Velocity-Rough-H12_12dof-v0 random-action rollout, {n} envs per MI355X" + (
-                ", CaT startup randomisation (BASELINE C5)" if args.task == "c5" else "")
         out = {
-            "metric": metric,
-            "value": value,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "ms_per_step": 1e3 * dt / K,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic: N(0,1) random actions, reset distribution of the Flat task (seeded)",
-            "config": {
-                "workload": workload,
-                "envs_per_gpu": n,
-                "global_envs": n * world,
-                "decimation": cfg.decimation,
-                "physics_dt": cfg.sim.dt,
-                "inner_steps": cfg.sim.inner_steps,
-                "implicit_penalty": bool(cfg.sim.implicit_penalty),
-                "parallelism": f"env-shard x{world}" + (f" + RCCL all-gather of the rollout every {rg.G} steps"
-                                                         if rg is not None and world > 1 else ""),
-            },
+            **line,
             "c4_rollout_allgather": c4 if c4 is not None or args.task in ROLLOUT_TASKS else {
                 "skipped": f"--task {args.task}: the compact records rebuild flat / rsl history rows only"},
-            "burn_in": B,
             "resets_in_window": resets_in_window,
             "replay_bit_exact": replay_exact,
             "roofline": {

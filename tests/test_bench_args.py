@@ -76,3 +76,42 @@ def test_kernel_source_hash_covers_the_headers(monkeypatch, tmp_path):
         f.write_bytes(old + b"\n// edit\n")
         assert B.source_sha256() != base, f.name
         f.write_bytes(old)
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    a = parse(monkeypatch, "--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    a = parse(monkeypatch, "--full", "--dump-outputs", "d")
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):  # ms_per_step is the window over --steps: an empty window has none
+        parse(monkeypatch, "--steps", "0")
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_budget(monkeypatch, tmp_path):
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    n = 37
+    arrays = {"obs_policy": torch.randn(n, 450, generator=g), "reward": torch.randn(n, generator=g),
+              "terminated": torch.rand(n, generator=g) < 0.5, "time_outs": (torch.rand(n, generator=g) < 0.5).to(torch.uint8)}
+    bench.dump_outputs(tmp_path / "all", arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape)
+        np.testing.assert_array_equal(a, v.float().numpy())
+    assert not (tmp_path / "all" / "env_ids.npy").exists()
+    # over the budget: the same seeded sample of envs for every array, ids beside them
+    per_env = (450 + 3) * 4 + 8
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * per_env + 5)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, arrays)
+    ids = np.load(tmp_path / "s1" / "env_ids.npy")
+    assert ids.dtype == np.float64 and len(ids) == 10 and len(set(ids)) == 10 and (np.diff(ids) > 0).all()
+    np.testing.assert_array_equal(ids, np.load(tmp_path / "s2" / "env_ids.npy"))
+    total = 0
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "s1" / f"{k}.npy")
+        np.testing.assert_array_equal(a, v.float().numpy()[ids.astype(int)])
+        total += a.nbytes
+    assert total + ids.nbytes <= bench.DUMP_BUDGET_BYTES

@@ -109,7 +109,7 @@ def test_two_rank_bench_rollout_allgather(tmp_path):
         log = open(tmp_path / f"rank{rank}.log", "w")
         cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--dist-backend", "gloo", "--envs", str(n),
                "--steps", str(K), "--warmup", str(W), "--burn-in", str(B), "--gather-every", "4",
-               "--no-cpu-baseline", "--rollout-decode", "--dump-rollout", str(dump)]
+               "--full", "--no-cpu-baseline", "--rollout-decode", "--dump-rollout", str(dump)]
         procs.append((subprocess.Popen(cmd, env=env, stdout=log, stderr=subprocess.STDOUT, cwd=str(ROOT)), log))
     try:
         for p, _ in procs:
@@ -186,7 +186,7 @@ def test_rccl_rollout_allgather_one_rank(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "1", "--rollout", "on",
            "--force-collective", "--envs", "64", "--steps", "30", "--warmup", "3", "--burn-in", "20",
-           "--gather-every", "8", "--no-cpu-baseline", "--dump-rollout", str(dump)]
+           "--gather-every", "8", "--full", "--no-cpu-baseline", "--dump-rollout", str(dump)]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, env=env, cwd=str(ROOT), capture_output=True, text=True, timeout=360)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -220,7 +220,7 @@ def test_c4_size_eight_rank_rehearsal(tmp_path):
         log = open(tmp_path / f"rank{rank}.log", "w")
         cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
                "--envs", str(n), "--steps", str(K), "--warmup", str(W), "--burn-in", str(B), "--rollout", "on",
-               "--no-cpu-baseline", "--rollout-decode", "--dump-rollout", str(dump)]
+               "--full", "--no-cpu-baseline", "--rollout-decode", "--dump-rollout", str(dump)]
         procs.append((subprocess.Popen(cmd, env=env, stdout=log, stderr=subprocess.STDOUT, cwd=str(ROOT)), log))
     try:
         for p, _ in procs:

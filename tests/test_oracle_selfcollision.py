@@ -6,7 +6,7 @@ foot as capsules, penalty contact between every left/right pair (DESIGN.md secti
 segments come from the URDF, no force while the legs are apart, action = reaction (zero net force and moment on
 the robot), a leg driven into the other is held off (and passes through without the model), random-action
 rollouts stay finite, and knee self-contact is an illegal contact (C12/rough_env_cfg.py:95-109)."""
-import xml.etree.ElementTree as ET
+import json
 from pathlib import Path
 
 import numpy as np
@@ -16,7 +16,8 @@ import oracle as O
 from h12env import H12FlatEnvCfg
 from h12env._abi import F as FI
 
-URDF = Path("/root/reference/packages/biped_assets/biped_assets/models/h12/h12_12dof.urdf")
+# the <collision> elements of h12_12dof.urdf's left_ankle_roll_link (origin xyz / rpy, cylinder length), stored
+FOOT_COLLIDERS = Path(__file__).resolve().parent / "golden" / "h12_foot_colliders.json"
 
 
 def crossed_state(model, roll, z=2.0):
@@ -41,14 +42,14 @@ def world_wrench(model, state, fext):
     return F, M
 
 
-@pytest.mark.skipif(not URDF.exists(), reason="reference URDF not present (build container only)")
 def test_rod_segments_follow_the_urdf(model):
-    root = ET.parse(URDF).getroot()
+    cols = json.loads(FOOT_COLLIDERS.read_text())["collisions"]
+    assert len(cols) == 4
     segs = []
-    for c in root.findall("link[@name='left_ankle_roll_link']/collision"):
-        xyz = np.array([float(v) for v in c.find("origin").get("xyz").split()])
-        rpy = np.array([float(v) for v in c.find("origin").get("rpy").split()])
-        L = float(c.find("geometry/cylinder").get("length"))
+    for c in cols:
+        xyz = np.array(c["xyz"])
+        rpy = np.array(c["rpy"])
+        L = c["cylinder"]["length"]
         ax = np.array([0, 1.0, 0]) if abs(rpy[0]) > 1 else np.array([1.0, 0, 0])
         segs.append(sorted([tuple(xyz - ax * L / 2), tuple(xyz + ax * L / 2)]))
     got = [sorted([tuple(np.array(model.foot_rods[r][e][:], dtype=np.float64)) for e in range(2)]) for r in range(4)]

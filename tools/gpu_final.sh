@@ -13,6 +13,6 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/${t
 tail -1 $o/${tag}_smoke.txt
 bash tools/profile.sh $tag > $o/${tag}_profile.log 2>&1 || { echo "profile failed"; tail -5 $o/${tag}_profile.log; exit 1; }
 echo "profile ok"
-timeout -k 10 300 python -u bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err || { echo "bench failed"; exit 1; }
 tail -c 600 $o/${tag}_bench.json
 exit $rc

@@ -8,12 +8,12 @@ o=gpurun_out
 bash tools/profile.sh $tag > $o/${tag}_profile.log 2>&1 || { echo "profile failed"; tail -20 $o/${tag}_profile.log; exit 1; }
 echo "profile ok"
 for t in rough c5 rsl cat; do
-  timeout -k 10 300 python -u bench.py --task $t --no-cpu-baseline > $o/${tag}_bench_$t.json 2> $o/${tag}_bench_$t.err || { echo "bench $t failed"; tail -20 $o/${tag}_bench_$t.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --task $t --no-cpu-baseline > $o/${tag}_bench_$t.json 2> $o/${tag}_bench_$t.err || { echo "bench $t failed"; tail -20 $o/${tag}_bench_$t.err; exit 1; }
   echo "bench $t ok"
 done
-timeout -k 10 300 python -u bench.py --rollout on --no-cpu-baseline > $o/${tag}_bench_rollout.json 2> $o/${tag}_bench_rollout.err || { echo "bench rollout failed"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --rollout on --no-cpu-baseline > $o/${tag}_bench_rollout.json 2> $o/${tag}_bench_rollout.err || { echo "bench rollout failed"; exit 1; }
 echo "bench rollout ok"
-timeout -k 10 300 python -u bench.py --rollout on --rollout-decode --no-cpu-baseline > $o/${tag}_bench_rollout_decode.json 2> $o/${tag}_bench_rollout_decode.err || { echo "bench rollout decode failed"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --rollout on --rollout-decode --no-cpu-baseline > $o/${tag}_bench_rollout_decode.json 2> $o/${tag}_bench_rollout_decode.err || { echo "bench rollout decode failed"; exit 1; }
 echo "bench rollout decode ok"
 timeout -k 10 600 python -u bench.py --mode train --no-cpu-baseline > $o/${tag}_bench_train.json 2> $o/${tag}_bench_train.err || { echo "bench train failed"; tail -20 $o/${tag}_bench_train.err; exit 1; }
 echo "bench train ok"

@@ -23,10 +23,10 @@ else:
 PY
 }
 for t in rsl cat rough c5; do
-  timeout -k 10 240 python3 -u bench.py --task $t --no-cpu-baseline > $o/bench_$t.json 2> $o/bench_$t.err || { echo "bench $t failed"; exit 1; }
+  timeout -k 10 240 python3 -u bench.py --full --task $t --no-cpu-baseline > $o/bench_$t.json 2> $o/bench_$t.err || { echo "bench $t failed"; exit 1; }
   line $t $o/bench_$t.json
 done
-timeout -k 10 240 python3 -u bench.py --rollout on --no-cpu-baseline > $o/bench_rollout.json 2> $o/bench_rollout.err || { echo "rollout failed"; exit 1; }
+timeout -k 10 240 python3 -u bench.py --full --rollout on --no-cpu-baseline > $o/bench_rollout.json 2> $o/bench_rollout.err || { echo "rollout failed"; exit 1; }
 line "rollout on" $o/bench_rollout.json
 timeout -k 10 240 python3 -u bench.py --steps 20 --warmup 5 > $o/bench_drv.json 2> $o/bench_drv.err || { echo "driver cmd failed"; exit 1; }
 line "driver cmd" $o/bench_drv.json

@@ -67,17 +67,23 @@ gym.register(
 )
 
 # h12_12dof/__init__.py:64-83: Constraints-as-Terminations (the env class returns the constraint termination
-# probability as dones; trained by the reference with CleanRL's PPO, which this build does not ship)
+# probability as dones; trained with the CleanRL PPO of h12env.cleanrl through scripts/train_cleanrl.py)
 gym.register(
     id="Isaac-Velocity-CaT-Flat-H12_12dof-v0",
     entry_point="h12env.cat:CaTEnv",
     disable_env_checker=True,
-    kwargs={"env_cfg_entry_point": "h12env.cfg:H12CaTEnvCfg"},
+    kwargs={
+        "env_cfg_entry_point": "h12env.cfg:H12CaTEnvCfg",
+        "clean_rl_cfg_entry_point": f"{agents.__name__}:H12_12dof_FlatCleanRlPPOCfg",
+    },
 )
 
 gym.register(
     id="Isaac-Velocity-CaT-Flat-H12_12dof-Play-v0",
     entry_point="h12env.cat:CaTEnv",
     disable_env_checker=True,
-    kwargs={"env_cfg_entry_point": "h12env.cfg:H12CaTEnvCfg_PLAY"},
+    kwargs={
+        "env_cfg_entry_point": "h12env.cfg:H12CaTEnvCfg_PLAY",
+        "clean_rl_cfg_entry_point": f"{agents.__name__}:H12_12dof_FlatCleanRlPPOCfg",
+    },
 )

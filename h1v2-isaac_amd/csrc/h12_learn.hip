@@ -23,6 +23,9 @@
 
 #include "../../include/h12learn.h"
 
+// the error record shared with h12_policy.hip (not part of the ABI)
+int h12_learn_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3), visibility("hidden")));
+
 namespace {
 
 constexpr int RMS_WAVES = 4;
@@ -316,3 +319,11 @@ int h12learn_gae_soft(const float* rewards, const float* values, const float* do
 const char* h12learn_last_error(void) { return g_learn_err; }
 
 }  // extern "C"
+
+int h12_learn_fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_learn_err, sizeof g_learn_err, fmt, ap);
+  va_end(ap);
+  return code;
+}

@@ -1,6 +1,6 @@
 """ctypes bindings of include/h12learn.h (the learner-side kernels of libh12env.so) on torch tensors.
 
-Both wrappers launch on the current HIP stream of the tensors' device, allocate only what they return and never
+The wrappers launch on the current HIP stream of the tensors' device, allocate only what they return and never
 synchronise, so they can run inside ``torch.cuda.graph`` capture."""
 from __future__ import annotations
 
@@ -11,7 +11,24 @@ import torch
 from ._abi import H12EnvError, load_library
 
 LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12learn_rms_forward",
-                 "h12learn_gae_soft", "h12learn_last_error"]
+                 "h12learn_gae_soft", "h12learn_mlp_max_width", "h12learn_mlp_packed_bytes", "h12learn_mlp_pack",
+                 "h12learn_mlp_forward", "h12learn_last_error"]
+
+MLP_MAX_NETS = 4
+MLP_MAX_LAYERS = 8
+MLP_NORM_NONE, MLP_NORM_VAR, MLP_NORM_STD = 0, 1, 2
+
+
+class MlpNet(C.Structure):
+    """h12learn_mlp_net"""
+    _fields_ = [("n_layers", C.c_int), ("dims", C.c_int * (MLP_MAX_LAYERS + 1)), ("W", C.c_void_p * MLP_MAX_LAYERS),
+                ("b", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class MlpDesc(C.Structure):
+    """h12learn_mlp_desc"""
+    _fields_ = [("n_nets", C.c_int), ("d_in", C.c_int), ("norm_kind", C.c_int), ("norm_eps", C.c_float),
+                ("norm_mean", C.c_void_p), ("norm_scale", C.c_void_p), ("nets", MlpNet * MLP_MAX_NETS)]
 
 _bound = None
 
@@ -35,6 +52,14 @@ def learn_library():
     lib.h12learn_rms_forward.restype = C.c_int
     lib.h12learn_gae_soft.argtypes = [vp] * 7 + [C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp]
     lib.h12learn_gae_soft.restype = C.c_int
+    lib.h12learn_mlp_max_width.argtypes = []
+    lib.h12learn_mlp_max_width.restype = C.c_int
+    lib.h12learn_mlp_packed_bytes.argtypes = [C.POINTER(MlpDesc)]
+    lib.h12learn_mlp_packed_bytes.restype = C.c_size_t
+    lib.h12learn_mlp_pack.argtypes = [C.POINTER(MlpDesc), vp, vp]
+    lib.h12learn_mlp_pack.restype = C.c_int
+    lib.h12learn_mlp_forward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.c_longlong, C.POINTER(C.c_void_p), vp]
+    lib.h12learn_mlp_forward.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -108,3 +133,69 @@ def gae_soft(rewards, values, dones, true_dones, next_value, next_done, next_tru
                                       float(gamma), float(gamma) * float(gae_lambda), T, N, adv.data_ptr(),
                                       ret.data_ptr(), _stream(rewards.device)), "h12learn_gae_soft")
     return adv, ret
+
+
+def mlp_max_width() -> int:
+    return learn_library().h12learn_mlp_max_width()
+
+
+def mlp_desc(nets, norm_kind: int = MLP_NORM_NONE, norm_mean: torch.Tensor | None = None,
+             norm_scale: torch.Tensor | None = None, norm_eps: float = 0.0) -> MlpDesc:
+    """The descriptor of ``nets``: a list of networks, each a list of (weight [out][in], bias [out]) tensor pairs.
+    Shapes and data pointers only; the caller keeps the tensors alive and in place."""
+    if not 1 <= len(nets) <= MLP_MAX_NETS:
+        raise ValueError(f"mlp_desc: {len(nets)} networks (1..{MLP_MAX_NETS})")
+    d = MlpDesc()
+    d.n_nets = len(nets)
+    d.d_in = int(nets[0][0][0].shape[1])
+    d.norm_kind, d.norm_eps = int(norm_kind), float(norm_eps)
+    if norm_kind != MLP_NORM_NONE:
+        d.norm_mean, d.norm_scale = norm_mean.data_ptr(), norm_scale.data_ptr()
+    for i, layers in enumerate(nets):
+        if not 1 <= len(layers) <= MLP_MAX_LAYERS:
+            raise ValueError(f"mlp_desc: network {i} has {len(layers)} layers (1..{MLP_MAX_LAYERS})")
+        net = d.nets[i]
+        net.n_layers = len(layers)
+        net.dims[0] = int(layers[0][0].shape[1])
+        for l, (w, b) in enumerate(layers):
+            if w.dim() != 2 or w.shape[1] != net.dims[l] or b.shape != (w.shape[0],):
+                raise ValueError(f"mlp_desc: network {i} layer {l}: weight {tuple(w.shape)}, bias {tuple(b.shape)}")
+            net.dims[l + 1] = int(w.shape[0])
+            net.W[l], net.b[l] = w.data_ptr(), b.data_ptr()
+    return d
+
+
+def mlp_packed_bytes(desc: MlpDesc) -> int:
+    lib = learn_library()
+    nbytes = lib.h12learn_mlp_packed_bytes(C.byref(desc))
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_mlp_packed_bytes")
+    return nbytes
+
+
+def mlp_pack(desc: MlpDesc, packed: torch.Tensor):
+    """Re-packs the weights ``desc`` points to into ``packed`` (one launch on the current stream)."""
+    lib = learn_library()
+    _f32(packed, "packed")
+    if packed.numel() * 4 < mlp_packed_bytes(desc):
+        raise ValueError("mlp_pack: packed is smaller than mlp_packed_bytes(desc)")
+    _check(lib, lib.h12learn_mlp_pack(C.byref(desc), packed.data_ptr(), _stream(packed.device)), "h12learn_mlp_pack")
+
+
+def mlp_forward(desc: MlpDesc, packed: torch.Tensor, x: torch.Tensor, out=None) -> tuple:
+    """One launch: the outputs ([n][d_out] each) of every network of ``desc`` on ``x`` [n][d_in]."""
+    lib = learn_library()
+    _f32(packed, "packed"), _f32(x, "x")
+    if x.dim() != 2 or x.shape[1] != desc.d_in or x.shape[0] < 1:
+        raise ValueError(f"mlp_forward: x {tuple(x.shape)} is not (n >= 1, {desc.d_in})")
+    n = x.shape[0]
+    widths = [desc.nets[i].dims[desc.nets[i].n_layers] for i in range(desc.n_nets)]
+    if out is None:
+        out = tuple(torch.empty((n, w), dtype=torch.float32, device=x.device) for w in widths)
+    for i, (y, w) in enumerate(zip(out, widths)):
+        if _f32(y, f"out[{i}]").shape != (n, w):
+            raise ValueError(f"mlp_forward: out[{i}] must be ({n}, {w})")
+    ys = (C.c_void_p * desc.n_nets)(*[y.data_ptr() for y in out])
+    _check(lib, lib.h12learn_mlp_forward(C.byref(desc), packed.data_ptr(), x.data_ptr(), n, ys, _stream(x.device)),
+           "h12learn_mlp_forward")
+    return tuple(out)

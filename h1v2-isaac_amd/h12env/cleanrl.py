@@ -207,6 +207,22 @@ class Agent(nn.Module):
         action, _, _, _ = self.get_action_and_value(self.obs_rms(x, update=False), deterministic=deterministic)
         return action
 
+    def inference_policy(self, fused: bool = False):
+        """The deterministic policy raw obs -> action mean (obs_rms read, not updated).  ``fused=True``: one
+        h12learn_mlp_forward launch (normaliser + actor_mean, h12env.policy.FusedMLP) packed from the parameters as
+        they are now; the default is the torch path."""
+        if fused:
+            from .policy import FusedMLP
+
+            f = FusedMLP([self.actor_mean], self.obs_rms)
+            return lambda x: f(x)[0]
+
+        def policy(x):
+            with torch.no_grad():
+                return self.actor_mean(self.obs_rms(x, update=False))
+
+        return policy
+
 
 # ---------------------------------------------------------------------------------------------- GAE
 def gae_soft_torch(rewards, values, dones, true_dones, next_value, next_done, next_true_done, gamma, gae_lambda):
@@ -249,14 +265,32 @@ class _Collector:
         self.agent = agent
         self.graphed = graphed
         self._graphs: dict = {}
+        self._fused = None
 
     def normalise(self, raw):
         with torch.no_grad():
             return self.agent.obs_rms(raw)
 
     def _act_body(self, obs):
+        from .policy import fused_collection_enabled
+
+        if fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled():
+            return self._act_body_fused(obs)
         action, logprob, _, value = self.agent.get_action_and_value(obs)
         return action, logprob, value.flatten()
+
+    def _act_body_fused(self, obs):
+        """H12_POLICY_FUSED=1: actor mean and critic value from one two-network h12learn_mlp_forward launch, the
+        weights re-packed in the same body (inside the captured graph, so never stale after an update); the sample
+        and the log-probability are get_action_and_value's."""
+        from .policy import FusedMLP
+
+        if self._fused is None:
+            self._fused = FusedMLP([self.agent.actor_mean, self.agent.critic])
+        mean, value = self._fused(obs, repack=True)
+        std = torch.exp(self.agent.actor_logstd.expand_as(mean))
+        action = mean + std * torch.randn_like(mean)
+        return action, Normal(mean, std, validate_args=False).log_prob(action).sum(1), value.flatten()
 
     def act(self, obs):
         if self.graphed:

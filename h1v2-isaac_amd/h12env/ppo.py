@@ -367,6 +367,11 @@ class PPO:
         if self._act_graph_ok(obs, critic_obs):
             return self._act_graphed(obs, critic_obs)
         self._obs, self._critic_obs = obs, critic_obs
+        if self._act_fused_ok(obs):  # eager collection on the fused forward: the graphed body, run directly
+            with torch.no_grad():
+                out = self._act_compute(obs, critic_obs)
+            self._actions, self._values, self._log_prob, self._mu, self._sigma = out
+            return self._actions
         self._actions = self.policy.act(obs).detach()
         self._values = self.policy.evaluate(critic_obs).detach()
         self._log_prob = self.policy.get_actions_log_prob(self._actions).detach()
@@ -379,14 +384,44 @@ class PPO:
         return (obs.is_cuda and not torch.is_grad_enabled() and os.environ.get("H12_PPO_GRAPH", "1") != "0"
                 and not getattr(self.policy, "is_recurrent", False))
 
+    def _act_fused_ok(self, obs) -> bool:
+        from .policy import fused_collection_enabled
+
+        return (fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled()
+                and not getattr(self.policy, "is_recurrent", False))
+
+    def _act_fused(self, obs, cobs):
+        """H12_POLICY_FUSED=1: actor mean and critic value from h12learn_mlp_forward, one two-network launch when
+        actor and critic read the same observation.  The weights are re-packed in the same body (and so inside the
+        captured graph): they can never be stale after an update."""
+        from .policy import FusedMLP
+
+        shared = cobs is obs
+        f = getattr(self, "_fused_mlp", None)
+        if f is None or f[0] != shared:
+            nets = ((FusedMLP([self.policy.actor, self.policy.critic]),) if shared else
+                    (FusedMLP([self.policy.actor]), FusedMLP([self.policy.critic])))
+            f = self._fused_mlp = (shared, nets)
+        if shared:
+            return f[1][0](obs, repack=True)
+        return f[1][0](obs, repack=True)[0], f[1][1](cobs, repack=True)[0]
+
     def _act_body(self):
-        mean = self.policy.actor(self._ga_obs)
+        self._ga_out = self._act_compute(self._ga_obs, self._ga_cobs)
+
+    def _act_compute(self, obs, cobs):
+        fused = self._act_fused_ok(obs)
+        if fused:
+            mean, values = self._act_fused(obs, cobs)
+        else:
+            mean = self.policy.actor(obs)
         std = self.policy._std(mean)
         # mean + std * N(0, 1): the same Normal(mean, std) sample as distribution.sample(), from randn (capturable)
         actions = mean + std * torch.randn_like(mean)
-        values = self.policy.critic(self._ga_cobs)
+        if not fused:
+            values = self.policy.critic(cobs)
         log_prob = Normal(mean, std).log_prob(actions).sum(dim=-1)
-        self._ga_out = (actions, values, log_prob, mean, std)
+        return actions, values, log_prob, mean, std
 
     def _act_graphed(self, obs, critic_obs):
         key = (tuple(obs.shape), tuple(critic_obs.shape), critic_obs is obs, obs.dtype)
@@ -832,10 +867,19 @@ class OnPolicyRunner:
         self.alg.broadcast_parameters()
         return d.get("infos")
 
-    def get_inference_policy(self, device=None):
+    def get_inference_policy(self, device=None, fused: bool = False):
+        """The deterministic policy obs -> action mean.  ``fused=True``: one h12learn_mlp_forward launch (normaliser +
+        actor, h12env.policy.FusedMLP) packed from the parameters as they are now; the default is the torch path."""
         self.eval_mode()
         if device is not None:
             self.alg.policy.to(device)
+        if fused:
+            from .policy import FusedMLP
+
+            if device is not None and self.empirical_normalization:
+                self.obs_normalizer.to(device)
+            f = FusedMLP([self.alg.policy.actor], self.obs_normalizer if self.empirical_normalization else None)
+            return lambda x: f(x)[0]
         policy = self.alg.policy.act_inference
         if self.empirical_normalization:
             if device is not None:

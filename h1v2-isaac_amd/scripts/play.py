@@ -28,6 +28,8 @@ def main(argv=None) -> int:
     ap.add_argument("--checkpoint", default="model_.*.pt")
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--fused", action="store_true",
+                    help="run the policy as one fused HIP launch (h12env.policy.FusedMLP) instead of torch modules")
     args = ap.parse_args(argv)
 
     import gymnasium as gym
@@ -51,7 +53,7 @@ def main(argv=None) -> int:
     env = RslRlVecEnvWrapper(gym.make(args.task, cfg=env_cfg))
     runner = OnPolicyRunner(env, agent_cfg.to_dict(), log_dir=None, device=args.device)
     runner.load(path)
-    policy = runner.get_inference_policy(device=args.device)
+    policy = runner.get_inference_policy(device=args.device, fused=args.fused)
     out = os.path.join(os.path.dirname(path), "exported")
     export_policy_as_jit(runner.alg.policy, runner.obs_normalizer, out, "policy.pt")
     write_env_yaml(env_cfg, os.path.join(out, "env.yaml"))

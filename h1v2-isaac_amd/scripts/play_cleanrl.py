@@ -31,6 +31,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--disable_fabric", action="store_true", default=False)
     ap.add_argument("--num_envs", type=int, default=None)
     ap.add_argument("--task", type=str, default="Isaac-Velocity-CaT-Flat-H12_12dof-Play-v0")
+    ap.add_argument("--fused", action="store_true", default=False,
+                    help="run the policy as one fused HIP launch (h12env.policy.FusedMLP) instead of torch modules")
     add_clean_rl_args(ap)
     AppLauncher.add_app_launcher_args(ap)
     return ap
@@ -96,9 +98,13 @@ def main(argv=None) -> int:
     obs = env.reset()[0]["policy"]
     export_agent(actor, obs.shape[-1], os.path.join(log_dir, "exported"))
 
+    fused = actor.inference_policy(fused=True) if args.fused else None
     for _ in range(args.video_length):
         with torch.no_grad():
-            actions, _, _, _ = actor.get_action_and_value(actor.obs_rms(obs, update=False), deterministic=True)
+            if fused is not None:
+                actions = fused(obs)
+            else:
+                actions, _, _, _ = actor.get_action_and_value(actor.obs_rms(obs, update=False), deterministic=True)
         next_obs, rewards, next_done, timeouts, info = env.step(actions)
         obs = next_obs["policy"]
     env.close()

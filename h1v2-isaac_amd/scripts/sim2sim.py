@@ -28,6 +28,8 @@ def main(argv=None) -> int:
     ap.add_argument("--command", type=float, nargs=3, default=[0.0, 0.0, 0.0])
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--log_dir", type=Path, default=None)
+    ap.add_argument("--fused", action="store_true",
+                    help="run policy.pt's actor and normaliser as one fused HIP launch (h12env.policy.FusedMLP)")
     args = ap.parse_args(argv)
 
     import torch
@@ -39,6 +41,11 @@ def main(argv=None) -> int:
 
     pcfg = yaml.safe_load((args.policy_dir / "env.yaml").read_text())
     policy = torch.jit.load(str(args.policy_dir / "policy.pt"), map_location=args.device).eval()
+    if args.fused:
+        from h12env.policy import FusedMLP
+
+        fused = FusedMLP.from_exported(policy, device=args.device)
+        policy = lambda x: fused(x)[0]  # noqa: E731
     cfg = mujoco_cfg()
     cfg.scene.num_envs = args.num_envs
     cfg.sim.device = args.device

@@ -1,7 +1,8 @@
-/* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip).
+/* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
- * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.
+ * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
+ * further down, is the policy's forward itself (h12env/policy.py): normaliser and every layer in one launch.
  *
  * Every compute entry point
  *   - takes raw device pointers and a HIP stream,
@@ -51,6 +52,56 @@ int h12learn_gae_soft(const float* rewards, const float* values, const float* do
                       const float* next_value, const float* next_done, const float* next_true_done,
                       float gamma, float gamma_lambda, int T, int N, float* advantages, float* returns,
                       void* stream);
+
+/* ---- fused policy MLP forward (csrc/h12_policy.hip): input normaliser + every Linear/ELU layer of up to
+ * H12LEARN_MLP_MAX_NETS networks over one shared input, in one launch, in exact fp32 (f32-input MFMA). */
+#define H12LEARN_MLP_MAX_NETS 4
+#define H12LEARN_MLP_MAX_LAYERS 8
+
+#define H12LEARN_MLP_NORM_NONE 0 /* x as it is */
+#define H12LEARN_MLP_NORM_VAR 1  /* (x - mean) / sqrt(scale + eps), scale = variance: cleanrl.RunningMeanStd */
+#define H12LEARN_MLP_NORM_STD 2  /* (x - mean) / (scale + eps), scale = std: ppo.EmpiricalNormalization */
+
+/* One network: n_layers Linear layers, ELU (alpha = 1) between them, the last one linear.  dims[0] is the input
+ * width (== desc.d_in), dims[l + 1] the output width of layer l.  W[l] is the torch weight [dims[l+1]][dims[l]]
+ * row-major contiguous fp32, b[l] the bias [dims[l+1]]; device pointers, read only. */
+typedef struct h12learn_mlp_net {
+  int n_layers;
+  int dims[H12LEARN_MLP_MAX_LAYERS + 1];
+  const float* W[H12LEARN_MLP_MAX_LAYERS];
+  const float* b[H12LEARN_MLP_MAX_LAYERS];
+} h12learn_mlp_net;
+
+/* norm_mean[d_in], norm_scale[d_in]: fp32 device vectors, read only, ignored with H12LEARN_MLP_NORM_NONE.  The
+ * division is a true (correctly rounded) division, as in torch. */
+typedef struct h12learn_mlp_desc {
+  int n_nets;
+  int d_in;
+  int norm_kind;
+  float norm_eps;
+  const float* norm_mean;
+  const float* norm_scale;
+  h12learn_mlp_net nets[H12LEARN_MLP_MAX_NETS];
+} h12learn_mlp_desc;
+
+/* The largest supported width of any layer, the input included. */
+int h12learn_mlp_max_width(void);
+
+/* Bytes of the packed weights of desc (shapes only: the pointers are not read); 0 with h12learn_last_error set when
+ * the shapes are invalid. */
+size_t h12learn_mlp_packed_bytes(const h12learn_mlp_desc* desc);
+
+/* One launch: copies every W / b of desc into the tiled, zero-padded layout the forward reads (packed: 16-byte
+ * aligned, h12learn_mlp_packed_bytes).  Run it after every change of the weights; it may be captured. */
+int h12learn_mlp_pack(const h12learn_mlp_desc* desc, float* packed, void* stream);
+
+/* One launch: y[i] ([n][d_out_i] fp32) = network i of desc applied to the normalised x ([n][d_in] contiguous fp32),
+ * from the weights in packed (the W / b pointers of desc are not read).  An output element is
+ * bias + sum_k h[k] W[j][k] accumulated as one fmaf chain whose k order depends on the layer's input width alone, so
+ * a row's result does not depend on n, on its position or on the other rows.  Networks wider than 512 need more
+ * than 64 KiB of LDS: the first such call of a process raises the kernel's limit (make it outside a capture). */
+int h12learn_mlp_forward(const h12learn_mlp_desc* desc, const float* packed, const float* x, long long n,
+                         float* const* y, void* stream);
 
 const char* h12learn_last_error(void);
 

@@ -1,6 +1,8 @@
 """GPU: the learner-side kernels (h12learn_rms_forward, h12learn_gae_soft) and the CleanRL PPO of the CaT task on
 the device: precision gates against fp64 restatements, bit-identity of the GAE with the fp32 torch loop, graphed
-collection == eager collection, the fused normaliser against the torch path, and an end-to-end run."""
+collection == eager collection, the fused normaliser against the torch path, and an end-to-end run.  The normaliser's
+fold is also run at the depth training reaches (RMS_DEPTH_SHAPES: a second fetch batch, the wide segment tree, a
+multi-chunk graph replay, count past 2^24); tests/test_rms_emulation.py shows on the CPU that these gates bite."""
 import sys
 from pathlib import Path
 
@@ -75,6 +77,55 @@ def _state(d, dev):
     return (torch.zeros(d, device=dev), torch.ones(d, device=dev), torch.ones((), device=dev))
 
 
+# The smallest shapes that reach each path of the last block's fold (R = 64 rows per chunk, 256 folding threads):
+# (n, d): (chunks, chunks per segment, segments, occupied segments).  tests/test_rms_emulation.py recomputes the
+# figures from rms_row_chunk(), so a change of R or of the block size fails there and the shapes are chosen anew.
+RMS_DEPTH_SHAPES = {
+    (2049, 64): (33, 9, 4, 4),         # a second fetch batch of one chunk; segments of 9, 9, 9, 6; last chunk one row
+    (4033, 70): (64, 16, 4, 4),        # two full fetch batches per segment (obs_rms at 4096 envs); 6-column tile
+    (1100, 5): (18, 1, 32, 18),        # dp = 8 > d; a tree of 18 occupied, then 14 empty segments
+    (2113, 12): (34, 3, 16, 12),       # dp = 16; the last segment is one chunk of one row
+    (16385, 1): (257, 2, 256, 129),    # the tree's top level merges the lone segment 128 into segment 0
+    (32768, 1): (512, 2, 256, 256),    # all 256 segments, the full 8-level tree (value_rms in training)
+}
+# d = 1 is rms_batches' column 1e3 + 1e-2 randn, whose gates (8u|mean| = 0.05 sigma) cannot see a lost row among
+# 16385: the lone segment of (16385, 1) may be dropped unnoticed (tests/test_rms_emulation.py).  So the d = 1
+# shapes run a second time on the zero-mean column (kind 3, the 1e-7 sigma gate), which is also what value_rms sees.
+RMS_DEPTH_CASES = [(n, d, None) for n, d in RMS_DEPTH_SHAPES] + [(n, d, 3) for n, d in RMS_DEPTH_SHAPES if d == 1]
+RMS_LATE_CASES = [(2049, 64, None), (16385, 1, None), (16385, 1, 3)]
+RMS_LATE_COUNT = 2.0 ** 24 + 2  # count + n is no longer exact in fp32: 4096 envs are here after ~170 iterations
+
+
+def rms_case_batches(n, d, kind=None, **kw):
+    """rms_batches(n, d), or for a d = 1 case with a column kind, that column of rms_batches(n, kind + 1)."""
+    if kind is None:
+        return rms_batches(n, d, **kw)
+    assert d == 1
+    return [np.ascontiguousarray(b[:, kind:kind + 1]) for b in rms_batches(n, kind + 1, **kw)]
+
+
+def rms_late_case(n, d, kind=None):
+    """A late-training state: fp32 (mean, var, count) with the column statistics of a first batch (the constant
+    column's variance set to 1e-4) and count = 2^24 + 2, and the three batches that follow."""
+    b = rms_case_batches(n, d, kind, calls=4, seed=11)
+    x0 = b[0].astype(np.float64)
+    v = x0.var(0)
+    return (x0.mean(0).astype(np.float32), np.where(v > 0, v, 1e-4).astype(np.float32), np.float32(RMS_LATE_COUNT),
+            b[1:])
+
+
+def check_rms_one_step(y, mean32, var32, count32, xb, before, what=""):
+    """One updating call from the fp32 state ``before`` = (mean, var, count): the fp64 reference restarts from that
+    state, so the drift of a long fp32 run (the reference algorithm's own property) is not under test.  The count
+    is the reference's fp32 ``count + batch_count``, bit for bit (the exact sum is not representable)."""
+    ref = Rms64(xb.shape[1])
+    ref.mean, ref.var, ref.count = before[0].astype(np.float64), before[1].astype(np.float64), float(before[2])
+    y64 = ref(xb, True)
+    check_rms_gates(y, mean32, var32, ref.count, y64, ref, what)
+    expect = np.float32(before[2]) + np.float32(xb.shape[0])
+    assert np.float32(count32).tobytes() == expect.tobytes(), (what, float(count32), float(expect))
+
+
 def test_rms_forward_against_fp64(gpu):
     from h12env import _learn
 
@@ -94,7 +145,7 @@ def test_rms_forward_against_fp64(gpu):
 def test_rms_forward_update_off_alias_and_reproducibility(gpu):
     from h12env import _learn
 
-    for n, d in [(2, 5), (65, 70), (300, 450), (130, 1)]:
+    for n, d in [(2, 5), (65, 70), (300, 450), (130, 1), (2049, 64), (16385, 1)]:
         b = rms_batches(n, d, calls=3, seed=5)
         mean, var, count = _state(d, gpu)
         ws = _learn.rms_workspace(n, d, gpu)
@@ -148,6 +199,99 @@ def test_running_mean_std_module_uses_the_kernel_in_place(gpu, monkeypatch):
     yt = t(x)
     assert float(t.count) == 66.0
     np.testing.assert_allclose(yt.cpu().numpy(), y64, rtol=1e-3, atol=0.1)  # sanity only: same statistic
+
+
+def test_rms_forward_against_fp64_at_fold_depth(gpu):
+    """The fold as training runs it: more than one fetch batch per segment, a wide segment tree, idle lanes past d
+    (RMS_DEPTH_CASES).  The gates are those of the shallow shapes: they do not depend on n."""
+    from h12env import _learn
+
+    for n, d, kind in RMS_DEPTH_CASES:
+        mean, var, count = _state(d, gpu)
+        ws = _learn.rms_workspace(n, d, gpu)
+        ref = Rms64(d)
+        for i, xb in enumerate(rms_case_batches(n, d, kind)):
+            x = torch.from_numpy(xb).to(gpu)
+            y = _learn.rms_forward(x, mean, var, count, EPS, True, ws)
+            y64 = ref(xb, True)
+            check_rms_gates(y.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy(), float(count), y64, ref,
+                            f"depth n={n} d={d}{'' if kind is None else f' kind {kind}'} call {i}")
+        assert int(ws[0]) == 0
+
+
+def test_rms_forward_from_a_late_training_state(gpu):
+    """count = 2^24 + 2 and statistics of the data's own scale: three one-step checks per shape."""
+    from h12env import _learn
+
+    for n, d, kind in RMS_LATE_CASES:
+        m0, v0, c0, batches = rms_late_case(n, d, kind)
+        mean, var = torch.from_numpy(m0).to(gpu), torch.from_numpy(v0).to(gpu)
+        count = torch.tensor(float(c0), device=gpu)
+        ws = _learn.rms_workspace(n, d, gpu)
+        for i, xb in enumerate(batches):
+            before = (mean.cpu().numpy(), var.cpu().numpy(), np.float32(float(count)))
+            y = _learn.rms_forward(torch.from_numpy(xb).to(gpu), mean, var, count, EPS, True, ws)
+            check_rms_one_step(y.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy(), float(count), xb, before,
+                               f"late n={n} d={d}{'' if kind is None else f' kind {kind}'} call {i}")
+        assert int(ws[0]) == 0
+
+
+def test_rms_forward_replayed_in_a_graph_at_fold_depth(gpu):
+    """64 chunks x 2 column tiles arrive on the counter inside a captured graph, as obs_rms does on every step of
+    a 4096-env collection: three replays on fresh batches are bit-identical to the eager sequence."""
+    from h12env import _learn
+
+    n, d = 4033, 70
+    b = rms_batches(n, d, calls=4, seed=7)
+    mean, var, count = _state(d, gpu)
+    ws = _learn.rms_workspace(n, d, gpu)
+    eager = []
+    for xb in b[1:]:
+        y = _learn.rms_forward(torch.from_numpy(xb).to(gpu), mean, var, count, EPS, True, ws)
+        eager.append([t.clone() for t in (y, mean, var, count)])
+    # static input, output, state and workspace; one warm-up call, then the state is put back
+    sx, (smean, svar, scount) = torch.from_numpy(b[0]).to(gpu), _state(d, gpu)
+    sy, sws = torch.empty_like(sx), _learn.rms_workspace(n, d, gpu)
+    _learn.rms_forward(sx, smean, svar, scount, EPS, True, sws, out=sy)
+    torch.cuda.synchronize()
+    assert int(sws[0]) == 0
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        _learn.rms_forward(sx, smean, svar, scount, EPS, True, sws, out=sy)
+    for t, s in zip((smean, svar, scount), _state(d, gpu)):
+        t.copy_(s)
+    for i, (xb, e) in enumerate(zip(b[1:], eager)):
+        sx.copy_(torch.from_numpy(xb))
+        g.replay()
+        for name, a, r in zip(("y", "mean", "var", "count"), (sy, smean, svar, scount), e):
+            assert torch.equal(a, r), (i, name)
+        assert int(sws[0]) == 0, i
+
+
+def test_rms_forward_reuses_a_larger_workspace(gpu):
+    """workspace_bytes >= need: one workspace sized for the largest depth shape, never zeroed again, serves the
+    d = 1 shapes from the largest n down and back up (stale partials of the larger runs stay behind the smaller
+    ones' range); bit-identical to exactly sized fresh workspaces."""
+    from h12env import _learn
+
+    need = _learn.learn_library().h12learn_rms_workspace_bytes
+    shared = _learn.rms_workspace(*max(RMS_DEPTH_SHAPES, key=lambda s: need(*s)), gpu)
+    seq = [32768, 16385, 130, 16385, 32768]
+    assert all(need(n, 1) < shared.numel() * 4 for n in seq)
+    runs = []
+    for fresh in (False, True):
+        mean, var, count = _state(1, gpu)
+        outs = []
+        for i, n in enumerate(seq):
+            ws = _learn.rms_workspace(n, 1, gpu) if fresh else shared
+            x = torch.from_numpy(rms_batches(n, 1, calls=1, seed=20 + i)[0]).to(gpu)
+            y = _learn.rms_forward(x, mean, var, count, EPS, True, ws)
+            assert int(ws[0]) == 0, (fresh, i)
+            outs.append([t.clone() for t in (y, mean, var, count)])
+        runs.append(outs)
+    for i, (a, r) in enumerate(zip(*runs)):
+        for name, s, t in zip(("y", "mean", "var", "count"), a, r):
+            assert torch.equal(s, t), (i, seq[i], name)
 
 
 # ---------------------------------------------------------------------------------------------- gae_soft
@@ -238,16 +382,16 @@ def _ppo_cfg(**kw):
     return H12_12dof_FlatCleanRlPPOCfg(**c)
 
 
-def _collect(tmp, graph: str):
+def _collect(tmp, graph: str, n_envs=64, **cfg):
     import os
 
     old = os.environ.get("H12_PPO_GRAPH")
     os.environ["H12_PPO_GRAPH"] = graph
     try:
-        env = _RecordRaw(_make_env(TASK))
+        env = _RecordRaw(_make_env(TASK, n=n_envs))
         rec = []
         torch.manual_seed(21)
-        agent = cleanrl.PPO(env, _ppo_cfg(), str(tmp / f"graph{graph}"),
+        agent = cleanrl.PPO(env, _ppo_cfg(**cfg), str(tmp / f"graph{graph}"),
                             on_step=lambda i, o, a, lp, v: rec.append([t.clone() for t in (o, a, lp, v)]))
         env.close()
     finally:
@@ -289,6 +433,43 @@ def test_fused_normaliser_against_torch_path(collection_runs, monkeypatch):
         worst = max(worst, ratio)
         assert ratio <= 1.0, (i, ratio)
     print(f"fused vs torch normaliser over the run: at most {worst:.3f} of the bound")
+
+
+DEEP_ENVS = 2112  # obs_rms: 33 chunks x 270 columns, 9 per segment; value_rms: 4 x 2112 rows, 132 occupied segments
+
+
+@pytest.fixture(scope="module")
+def deep_collection_runs(gpu, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("cleanrl_collect_deep")
+    return [_collect(tmp, graph, n_envs=DEEP_ENVS, minibatch_size=DEEP_ENVS) for graph in ("1", "0")]
+
+
+def test_graphed_collection_equals_eager_past_one_chunk(deep_collection_runs):
+    """The multi-chunk arrival counter replayed inside the collection graph, as in training."""
+    (ag, rg, _), (ae, re_, _) = deep_collection_runs
+    assert len(rg) == len(re_) == 8 and rg[0][0].shape[0] == DEEP_ENVS
+    for i, (g, e) in enumerate(zip(rg, re_)):
+        for name, a, b in zip(("obs", "action", "logprob", "value"), g, e):
+            assert torch.equal(a, b), (i, name, float((a - b).abs().max()))
+    for k in ("running_mean", "running_var", "count"):
+        assert torch.equal(getattr(ag.obs_rms, k), getattr(ae.obs_rms, k)), k
+        assert torch.equal(getattr(ag.value_rms, k), getattr(ae.value_rms, k)), k
+    assert float(ag.obs_rms.count) == 1 + 9 * DEEP_ENVS
+
+
+def test_fused_normaliser_against_torch_path_past_one_chunk(deep_collection_runs, monkeypatch):
+    (_, rec, raw), _ = deep_collection_runs
+    monkeypatch.setenv("H12_CLEANRL_FUSED", "0")
+    t = cleanrl.RunningMeanStd(shape=(raw[0].shape[1],)).to(raw[0].device)
+    worst = 0.0
+    for i, (r, (o, _, _, _)) in enumerate(zip(raw, rec)):
+        yt = t(r).double()
+        sigma = torch.sqrt(t.running_var.double() + EPS)
+        bound = 8 * U * (t.running_mean.double().abs() / sigma + yt.abs()) + 1e-7
+        ratio = float(((o.double() - yt).abs() / bound).max())
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, (i, ratio)
+    print(f"fused vs torch normaliser over the {DEEP_ENVS}-env run: at most {worst:.3f} of the bound")
 
 
 def test_cleanrl_ppo_end_to_end_on_the_cat_task(gpu, tmp_path):

@@ -4618,6 +4618,297 @@ __global__ void __launch_bounds__(BLOCK) physics_kernel(KParams P, Workspace W, 
   store_env<K>(P, W, e, leg, s);
 }
 
+// ------------------------------------------------------------------ safety monitor (h12env_step_physics_monitored)
+// physics_kernel's loop with an observer: per substep every lane records its 6 joints and its foot into the caller's
+// [H12_MON_WORDS][n] accumulators (and, for traced envs, the raw record).  The lane pair owns the env's words, so there
+// are no atomics; signed values are exposed in real (unmirrored) joint signs.  REG keeps the lane's 79 accumulator words
+// in registers over the whole call, !REG reads / modifies / writes them (L2-resident) every substep.
+struct MonArgs {
+  uint32_t* mon;      // [H12_MON_WORDS][n]
+  const float* lim;   // [H12_MON_LIMIT_WORDS]
+  float* trace;       // [n_substeps][n_trace][H12_TRACE_WORDS] or null
+  int trace_env0, n_trace;
+};
+struct MonLane {      // one lane's accumulators: its leg's joints, its foot, and (left lane) the env's words
+  int pos_viol[NL], tau_sat[NL], qd_viol[NL];
+  float pos_ex[NL], tau_max[NL], qd_max[NL], tr_sum[NL], tr_max[NL], qr_sum[NL], qr_max[NL], tau_prev[NL], q_prev[NL];
+  int f_viol, contact;
+  float f_max, f_sum, fp_sum, fp_max;
+};
+H12_DEV float mon_ldf(const MonArgs& M, int n, int w, int e) { return __uint_as_float(M.mon[(size_t)w * n + e]); }
+H12_DEV int mon_ldi(const MonArgs& M, int n, int w, int e) { return (int)M.mon[(size_t)w * n + e]; }
+H12_DEV void mon_stf(const MonArgs& M, int n, int w, int e, float x) { M.mon[(size_t)w * n + e] = __float_as_uint(x); }
+H12_DEV void mon_sti(const MonArgs& M, int n, int w, int e, int x) { M.mon[(size_t)w * n + e] = (uint32_t)x; }
+H12_DEV void mon_load_joint(const MonArgs& M, int n, int e, int leg, int k, MonLane& a) {
+  {
+    const int j = NL * leg + k;
+    a.pos_viol[k] = mon_ldi(M, n, H12_MON_POS_VIOL_COUNT + j, e);
+    a.pos_ex[k] = mon_ldf(M, n, H12_MON_POS_EXCESS_MAX + j, e);
+    a.tau_max[k] = mon_ldf(M, n, H12_MON_TAU_ABS_MAX + j, e);
+    a.tau_sat[k] = mon_ldi(M, n, H12_MON_TAU_SAT_COUNT + j, e);
+    a.qd_max[k] = mon_ldf(M, n, H12_MON_QD_ABS_MAX + j, e);
+    a.qd_viol[k] = mon_ldi(M, n, H12_MON_QD_VIOL_COUNT + j, e);
+    a.tr_sum[k] = mon_ldf(M, n, H12_MON_TAU_RATE_SUM + j, e);
+    a.tr_max[k] = mon_ldf(M, n, H12_MON_TAU_RATE_MAX + j, e);
+    a.qr_sum[k] = mon_ldf(M, n, H12_MON_Q_RATE_SUM + j, e);
+    a.qr_max[k] = mon_ldf(M, n, H12_MON_Q_RATE_MAX + j, e);
+    a.tau_prev[k] = mon_ldf(M, n, H12_MON_TAU_PREV + j, e);
+    a.q_prev[k] = mon_ldf(M, n, H12_MON_Q_PREV + j, e);
+  }
+}
+H12_DEV void mon_store_joint(const MonArgs& M, int n, int e, int leg, int k, const MonLane& a) {
+  {
+    const int j = NL * leg + k;
+    mon_sti(M, n, H12_MON_POS_VIOL_COUNT + j, e, a.pos_viol[k]);
+    mon_stf(M, n, H12_MON_POS_EXCESS_MAX + j, e, a.pos_ex[k]);
+    mon_stf(M, n, H12_MON_TAU_ABS_MAX + j, e, a.tau_max[k]);
+    mon_sti(M, n, H12_MON_TAU_SAT_COUNT + j, e, a.tau_sat[k]);
+    mon_stf(M, n, H12_MON_QD_ABS_MAX + j, e, a.qd_max[k]);
+    mon_sti(M, n, H12_MON_QD_VIOL_COUNT + j, e, a.qd_viol[k]);
+    mon_stf(M, n, H12_MON_TAU_RATE_SUM + j, e, a.tr_sum[k]);
+    mon_stf(M, n, H12_MON_TAU_RATE_MAX + j, e, a.tr_max[k]);
+    mon_stf(M, n, H12_MON_Q_RATE_SUM + j, e, a.qr_sum[k]);
+    mon_stf(M, n, H12_MON_Q_RATE_MAX + j, e, a.qr_max[k]);
+    mon_stf(M, n, H12_MON_TAU_PREV + j, e, a.tau_prev[k]);
+    mon_stf(M, n, H12_MON_Q_PREV + j, e, a.q_prev[k]);
+  }
+}
+H12_DEV void mon_load_foot(const MonArgs& M, int n, int e, int leg, MonLane& a) {
+  a.f_max = mon_ldf(M, n, H12_MON_FORCE_MAX + leg, e);
+  a.f_sum = mon_ldf(M, n, H12_MON_FORCE_SUM + leg, e);
+  a.f_viol = mon_ldi(M, n, H12_MON_FORCE_VIOL_COUNT + leg, e);
+  // the env's words: the left lane's (the right lane's copies are never stored)
+  a.contact = mon_ldi(M, n, H12_MON_CONTACT_SUBSTEPS, e);
+  a.fp_sum = mon_ldf(M, n, H12_MON_FORCE_PAIR_SUM, e);
+  a.fp_max = mon_ldf(M, n, H12_MON_FORCE_PAIR_MAX, e);
+}
+H12_DEV void mon_store_foot(const MonArgs& M, int n, int e, int leg, const MonLane& a, int substeps) {
+  mon_stf(M, n, H12_MON_FORCE_MAX + leg, e, a.f_max);
+  mon_stf(M, n, H12_MON_FORCE_SUM + leg, e, a.f_sum);
+  mon_sti(M, n, H12_MON_FORCE_VIOL_COUNT + leg, e, a.f_viol);
+  if (leg == 0) {
+    mon_sti(M, n, H12_MON_SUBSTEPS, e, substeps);
+    mon_sti(M, n, H12_MON_CONTACT_SUBSTEPS, e, a.contact);
+    mon_stf(M, n, H12_MON_FORCE_PAIR_SUM, e, a.fp_sum);
+    mon_stf(M, n, H12_MON_FORCE_PAIR_MAX, e, a.fp_max);
+  }
+}
+// the joint part of a record: the state BEFORE the substep and the torque applied in it.  Every sum is one separately
+// rounded fp32 add per substep (no contraction), so a float32 loop over the trace reproduces the words bit for bit
+H12_DEV void mon_update_joint(const KParams& P, const MonArgs& M, int leg, int k, const float* q, const float* qd,
+                              const float* tau, bool first, MonLane& a) {
+#pragma clang fp contract(off)
+  const float sg = leg ? -1.f : 1.f;
+  {
+    const float js = jsign(k, sg);
+    // limits in the lane's (mirrored) frame: QLO / QHI are the left leg's, and the mirror maps the right leg's range
+    // [-QHI, -QLO] onto them, so no sign enters the test
+    const float ql = q[k];
+    a.pos_viol[k] += (ql < h12m::QLO[k] || ql > h12m::QHI[k]) ? 1 : 0;
+    a.pos_ex[k] = fmaxf(a.pos_ex[k], fmaxf(fmaxf(h12m::QLO[k] - ql, ql - h12m::QHI[k]), 0.f));
+    const float ta = fabsf(tau[k]), va = fabsf(qd[k]);
+    a.tau_max[k] = fmaxf(a.tau_max[k], ta);
+    a.tau_sat[k] += ta >= P.elim[k] ? 1 : 0;
+    a.qd_max[k] = fmaxf(a.qd_max[k], va);
+    const float vl = M.lim[H12_MON_LIMIT_QD + NL * leg + k];
+    a.qd_viol[k] += (vl > 0.f && va > vl) ? 1 : 0;
+    const float tr = js * tau[k], qr = js * ql;  // real signs
+    const float dt_ = first ? 0.f : fabsf(tr - a.tau_prev[k]);
+    const float dq_ = first ? 0.f : fabsf(qr - a.q_prev[k]);
+    a.tr_sum[k] = a.tr_sum[k] + dt_;
+    a.tr_max[k] = fmaxf(a.tr_max[k], dt_);
+    a.qr_sum[k] = a.qr_sum[k] + dq_;
+    a.qr_max[k] = fmaxf(a.qr_max[k], dq_);
+    a.tau_prev[k] = tr;
+    a.q_prev[k] = qr;
+  }
+}
+// the foot part: fn = this lane's foot force norm of the substep, fo = the other lane's
+H12_DEV void mon_update_foot(const MonArgs& M, float fn, float fo, MonLane& a) {
+#pragma clang fp contract(off)
+  a.f_max = fmaxf(a.f_max, fn);
+  a.f_sum = a.f_sum + fn;
+  a.f_viol += fn > M.lim[H12_MON_LIMIT_FORCE] ? 1 : 0;
+  if (fn != 0.f || fo != 0.f) {  // left lane: fn = left, fo = right
+    const float pair = fn + fo;
+    a.contact += 1;
+    a.fp_sum = a.fp_sum + pair;
+    a.fp_max = fmaxf(a.fp_max, pair);
+  }
+}
+
+// every value of a copied pre-step state made opaque to the optimiser (see physics_monitor_kernel)
+H12_DEV void mon_opaque(Base& b, Leg& l, const float* tau, float* tau2) {
+  auto op = [](float& x) { asm volatile("" : "+v"(x)); };
+  for (int i = 0; i < 3; ++i) { op(b.pos[i]); op(b.vlin[i]); op(b.wang[i]); }
+  for (int i = 0; i < 4; ++i) op(b.quat[i]);
+  for (int k = 0; k < NL; ++k) {
+    op(l.q[k]);
+    op(l.qd[k]);
+    tau2[k] = tau[k];
+    op(tau2[k]);
+  }
+  for (int q = 0; q < H12_NFOOT_PTS; ++q) { op(l.anc[q][0]); op(l.anc[q][1]); }
+  asm volatile("" : "+v"(l.cmask));
+  op(l.mus);
+  op(l.mud);
+  op(l.dmass);
+}
+
+template <int K, bool REG>
+__global__ void __launch_bounds__(BLOCK) physics_monitor_kernel(KParams P, Workspace W, StepArgs A, MonArgs M) {
+  const int lane_pair = threadIdx.x >> 1;
+  const int leg = threadIdx.x & 1;
+  const float sg = leg ? -1.f : 1.f;
+  const int e = lane_pair + blockIdx.x * ENVS_PER_BLOCK;
+  if (e >= W.n) return;
+  const int n = W.n;
+  EnvSt s;
+  load_env<K>(P, W, e, leg, s);
+  float qr[NL];
+  for (int k = 0; k < NL; ++k) qr[k] = jsign(k, sg) * A.q_ref[(size_t)e * NJ + NL * leg + k];
+  const float wgt = frcp((float)P.inner);
+  int substeps = mon_ldi(M, n, H12_MON_SUBSTEPS, e);
+  const bool traced = M.trace && e >= M.trace_env0 && e < M.trace_env0 + M.n_trace;
+  MonLane acc;
+  if (REG) {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) mon_load_joint(M, n, e, leg, k, acc);
+    mon_load_foot(M, n, e, leg, acc);
+  }
+  for (int st = 0; st < A.n_substeps; ++st) {
+    float tau[NL];
+    for (int k = 0; k < NL; ++k) {
+      float v = P.kp[k] * (qr[k] - s.lg.q[k]) - P.kd[k] * s.lg.qd[k];
+      tau[k] = fminf(fmaxf(v, -P.elim[k]), P.elim[k]);
+    }
+    // ---- observer, joint part: the pre-step state and the torque of this substep
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {  // joint by joint: 12 words live at a time without REG
+      if (!REG) mon_load_joint(M, n, e, leg, k, acc);
+      mon_update_joint(P, M, leg, k, s.lg.q, s.lg.qd, tau, substeps == 0, acc);
+      if (!REG) mon_store_joint(M, n, e, leg, k, acc);
+    }
+    float* rec = nullptr;
+    if (traced) {
+      rec = M.trace + ((size_t)st * M.n_trace + (e - M.trace_env0)) * H12_TRACE_WORDS;
+      if (leg == 0) {
+        for (int i = 0; i < 3; ++i) rec[H12_TRACE_POS + i] = s.b.pos[i];
+        for (int i = 0; i < 4; ++i) rec[H12_TRACE_QUAT + i] = s.b.quat[i];
+        for (int i = 0; i < 3; ++i) rec[H12_TRACE_VLIN + i] = s.b.vlin[i];
+        for (int i = 0; i < 3; ++i) rec[H12_TRACE_WANG + i] = s.b.wang[i];
+      }
+#pragma unroll
+      for (int k = 0; k < NL; ++k) {
+        const float js = jsign(k, sg);
+        rec[H12_TRACE_Q + NL * leg + k] = js * s.lg.q[k];
+        rec[H12_TRACE_QD + NL * leg + k] = js * s.lg.qd[k];
+        rec[H12_TRACE_TAU + NL * leg + k] = js * tau[k];
+      }
+    }
+    // The force report comes from a second evaluation of the substep on an opaque copy of the pre-step state.  In
+    // physics_kernel the report is dead code; keeping it alive in the evaluation that advances the state changes how
+    // the compiler forms that evaluation's fused multiply-adds, and the state no longer matches h12env_step_physics
+    // bit for bit (measured).  The copy's values pass through empty asm statements, so nothing of
+    // the two evaluations can be merged, and the first one below is physics_kernel's statement with a dead report.
+    Base b2 = s.b;
+    Leg l2 = s.lg;
+    float tau2[NL];
+    mon_opaque(b2, l2, tau, tau2);
+    Forces fr = {};
+    for (int it = 0; it < P.inner; ++it) inner_step_1w<K>(P, leg, s.b, s.lg, tau, P.h, fr, s.origin);
+    Forces fr2 = {};
+    for (int it = 0; it < P.inner; ++it) inner_step_1w<K>(P, leg, b2, l2, tau2, P.h, fr2, s.origin);
+    // ---- observer, foot part: the contact sensor's net force of this substep (mean over the inner steps)
+    const float fn = fsqrt(fr2.foot[0] * fr2.foot[0] + fr2.foot[1] * fr2.foot[1] + fr2.foot[2] * fr2.foot[2]) * wgt;
+    const float fo = pair_swap(fn);
+    if (!REG) mon_load_foot(M, n, e, leg, acc);
+    mon_update_foot(M, fn, fo, acc);
+    substeps += 1;
+    if (!REG) mon_store_foot(M, n, e, leg, acc, substeps);
+    if (traced) rec[H12_TRACE_FORCE + leg] = fn;
+  }
+  if (REG) {
+#pragma unroll
+    for (int k = 0; k < NL; ++k) mon_store_joint(M, n, e, leg, k, acc);
+    mon_store_foot(M, n, e, leg, acc, substeps);
+  }
+  store_env<K>(P, W, e, leg, s);
+}
+
+// Fold of the monitor over the envs (h12env_monitor_reduce): stage 0, block b folds its chunk of envs in env order, one
+// thread per summary word, into partial record 1 + b; stage 1 (one block) folds the partial records in block order into
+// record 0.  Fixed order, no atomics, no waiting: the result is the same bits on every run.
+constexpr int RED_BLOCK = 192;
+static_assert(RED_BLOCK >= H12_SUM_WORDS, "one thread per summary word");
+struct RedArgs {
+  const uint32_t* mon;
+  unsigned long long* out;  // [1 + nb][H12_SUM_WORDS]
+  int n, chunk, nb;
+};
+enum { RK_COUNT = 0, RK_MAX = 1, RK_SUM = 2, RK_ZERO = 3 };
+H12_DEV int red_kind(int w) {
+  if (w < H12_MON_POS_EXCESS_MAX) return RK_COUNT;
+  if (w < H12_MON_TAU_SAT_COUNT) return RK_MAX;
+  if (w < H12_MON_QD_ABS_MAX) return RK_COUNT;
+  if (w < H12_MON_QD_VIOL_COUNT) return RK_MAX;
+  if (w < H12_MON_TAU_RATE_SUM) return RK_COUNT;
+  if (w < H12_MON_TAU_RATE_MAX) return RK_SUM;
+  if (w < H12_MON_Q_RATE_SUM) return RK_MAX;
+  if (w < H12_MON_Q_RATE_MAX) return RK_SUM;
+  if (w < H12_MON_TAU_PREV) return RK_MAX;
+  if (w < H12_MON_FORCE_MAX) return RK_ZERO;
+  if (w < H12_MON_FORCE_SUM) return RK_MAX;
+  if (w < H12_MON_FORCE_VIOL_COUNT) return RK_SUM;
+  if (w < H12_MON_FORCE_PAIR_SUM) return RK_COUNT;
+  if (w < H12_MON_FORCE_PAIR_MAX) return RK_SUM;
+  if (w < H12_MON_WORDS) return RK_MAX;
+  return RK_COUNT;
+}
+H12_DEV bool red_any(const RedArgs& R, int w0, int cnt, int e) {
+  bool v = false;
+  for (int i = 0; i < cnt; ++i) v = v || R.mon[(size_t)(w0 + i) * R.n + e] != 0u;
+  return v;
+}
+template <int STAGE>
+__global__ void __launch_bounds__(RED_BLOCK) monitor_reduce_kernel(RedArgs R) {
+#pragma clang fp contract(off)
+  const int w = threadIdx.x;
+  if (w >= H12_SUM_WORDS) return;
+  const int kind = red_kind(w);
+  long long ci = 0;
+  double cd = 0.0;
+  if (STAGE == 0) {
+    const int e0 = blockIdx.x * R.chunk, e1 = min(R.n, e0 + R.chunk);
+    for (int e = e0; e < e1; ++e) {
+      if (w < H12_MON_WORDS) {
+        const uint32_t u = R.mon[(size_t)w * R.n + e];
+        if (kind == RK_COUNT) ci += (long long)(int)u;
+        else if (kind == RK_MAX) cd = e == e0 ? (double)__uint_as_float(u) : fmax(cd, (double)__uint_as_float(u));
+        else if (kind == RK_SUM) cd = cd + (double)__uint_as_float(u);
+      } else {
+        const bool pv = red_any(R, H12_MON_POS_VIOL_COUNT, NJ, e), fv = red_any(R, H12_MON_FORCE_VIOL_COUNT, 2, e),
+                   vv = red_any(R, H12_MON_QD_VIOL_COUNT, NJ, e);
+        ci += w == H12_SUM_ENVS_POS_VIOL ? pv : w == H12_SUM_ENVS_FORCE_VIOL ? fv : w == H12_SUM_ENVS_VEL_VIOL ? vv
+              : w == H12_SUM_ENVS_ANY_VIOL ? (pv || fv || vv) : true;
+      }
+    }
+  } else {
+    for (int b = 0; b < R.nb; ++b) {
+      const unsigned long long u = R.out[(size_t)(1 + b) * H12_SUM_WORDS + w];
+      if (kind == RK_COUNT) ci += (long long)u;
+      else if (kind == RK_MAX) cd = b == 0 ? __longlong_as_double((long long)u) : fmax(cd, __longlong_as_double((long long)u));
+      else if (kind == RK_SUM) cd = cd + __longlong_as_double((long long)u);
+    }
+  }
+  const unsigned long long res = kind == RK_COUNT ? (unsigned long long)ci
+                                 : kind == RK_ZERO ? 0ull : (unsigned long long)__double_as_longlong(cd);
+  R.out[(size_t)(STAGE == 0 ? 1 + blockIdx.x : 0) * H12_SUM_WORDS + w] = res;
+}
+// envs per stage-0 block: 64, more once that would need over 1024 partial records
+inline int red_chunk(int n) { return std::max(64, (n + 1023) / 1024); }
+inline int red_blocks(int n) { return (n + red_chunk(n) - 1) / red_chunk(n); }
+
 // ------------------------------------------------------------------ rollout records (C4: all-gathered rollouts)
 // Step record of one shard (h12env_rollout_layout): frames f32 [n][45], actions f32 [n][12], rewards f32 [n],
 // terminated u8 [n], truncated u8 [n], each section 256-B aligned; gathered in chunks of G steps (see the header).
@@ -5521,6 +5812,75 @@ int h12env_step_physics(h12env* hh, const float* q_ref, int n_substeps, void* st
   A.q_ref = q_ref;
   A.n_substeps = n_substeps;
   LAUNCH_K(physics_kernel, dim3(n_blocks(h)), dim3(BLOCK), 0, (hipStream_t)stream, h->P, h->W, A);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+constexpr bool MON_REGS_DEFAULT = true;
+// largest env count of one handle (h12env_create's bound)
+constexpr int MAX_ENVS = 0x7FFFFFFF / (H12_NF_FLOAT * 4);
+
+int h12env_monitor_layout(int n_envs, int n_trace, int n_substeps, size_t* monitor_bytes, size_t* trace_bytes,
+                          size_t* summary_bytes) {
+  if (n_envs < 1 || n_envs > MAX_ENVS) return set_err(H12_E_ARG, "n_envs must be in 1..%d (got %d)", MAX_ENVS, n_envs);
+  if (n_trace < 0 || n_trace > n_envs) return set_err(H12_E_ARG, "n_trace must be in 0..n_envs (got %d)", n_trace);
+  if (n_substeps < 0) return set_err(H12_E_ARG, "n_substeps must be >= 0 (got %d)", n_substeps);
+  if (monitor_bytes) *monitor_bytes = (size_t)H12_MON_WORDS * n_envs * 4;
+  if (trace_bytes) *trace_bytes = (size_t)n_substeps * n_trace * H12_TRACE_WORDS * 4;
+  if (summary_bytes) *summary_bytes = (size_t)(1 + red_blocks(n_envs)) * H12_SUM_WORDS * 8;
+  return 0;
+}
+
+int h12env_step_physics_monitored(h12env* hh, const float* q_ref, int n_substeps, void* monitor, const float* limits,
+                                  float* trace, int trace_env0, int n_trace, void* stream) {
+  Handle* h = (Handle*)hh;
+  // every argument is validated before the first HIP call; what needs no handle first
+  if (!q_ref) return set_err(H12_E_ARG, "q_ref is required");
+  if (n_substeps < 0) return set_err(H12_E_ARG, "n_substeps must be >= 0 (got %d)", n_substeps);
+  if (!monitor) return set_err(H12_E_ARG, "monitor is required");
+  if (!limits) return set_err(H12_E_ARG, "limits is required");
+  if (n_trace < 0) return set_err(H12_E_ARG, "n_trace must be >= 0 (got %d)", n_trace);
+  if (trace_env0 < 0) return set_err(H12_E_ARG, "trace_env0 must be >= 0 (got %d)", trace_env0);
+  if (n_trace > 0 && !trace) return set_err(H12_E_ARG, "trace is required when n_trace > 0");
+  if ((long long)trace_env0 + n_trace > MAX_ENVS)
+    return set_err(H12_E_ARG, "trace range [trace_env0 %d, + n_trace %d) ends beyond n", trace_env0, n_trace);
+  if (!h) return set_err(H12_E_ARG, "null handle");
+  if (trace_env0 + n_trace > h->W.n)
+    return set_err(H12_E_ARG, "trace range [trace_env0 %d, + n_trace %d) ends beyond n = %d", trace_env0, n_trace, h->W.n);
+  StepArgs A = {};
+  A.q_ref = q_ref;
+  A.n_substeps = n_substeps;
+  MonArgs M = {(uint32_t*)monitor, limits, n_trace > 0 ? trace : nullptr, trace_env0, n_trace};
+  const dim3 grid(n_blocks(h)), blk(BLOCK);
+  hipStream_t sm = (hipStream_t)stream;
+  // accumulators in registers over the call, or read-modify-write per substep (environment variable H12_MON_REGS, read
+  // once; the default is the measured choice).  Same bits either way.
+  static const bool reg = [] {
+    const char* v = getenv("H12_MON_REGS");
+    return v ? v[0] == '1' : MON_REGS_DEFAULT;
+  }();
+  const int lvl = feature_level(h->P);
+#define MON_LAUNCH(K_, R_) \
+  hipLaunchKernelGGL((physics_monitor_kernel<K_, R_>), grid, blk, 0, sm, h->P, h->W, A, M)
+  if (reg) {
+    if (lvl == 0) MON_LAUNCH(0, true); else if (lvl == 1) MON_LAUNCH(1, true); else MON_LAUNCH(2, true);
+  } else {
+    if (lvl == 0) MON_LAUNCH(0, false); else if (lvl == 1) MON_LAUNCH(1, false); else MON_LAUNCH(2, false);
+  }
+#undef MON_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int h12env_monitor_reduce(h12env* hh, const void* monitor, void* summary, void* stream) {
+  Handle* h = (Handle*)hh;
+  if (!monitor) return set_err(H12_E_ARG, "monitor is required");
+  if (!summary) return set_err(H12_E_ARG, "summary is required");
+  if (!h) return set_err(H12_E_ARG, "null handle");
+  RedArgs R = {(const uint32_t*)monitor, (unsigned long long*)summary, h->W.n, red_chunk(h->W.n), red_blocks(h->W.n)};
+  hipLaunchKernelGGL(monitor_reduce_kernel<0>, dim3(R.nb), dim3(RED_BLOCK), 0, (hipStream_t)stream, R);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(monitor_reduce_kernel<1>, dim3(1), dim3(RED_BLOCK), 0, (hipStream_t)stream, R);
   HIP_TRY(hipGetLastError());
   return 0;
 }

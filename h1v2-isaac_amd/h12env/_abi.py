@@ -43,6 +43,22 @@ NF_FLOAT = 143
 I = dict(EPLEN=(0, 1), PACK=(1, 1), TERRAIN=(2, 1))
 NF_INT = 3
 
+# safety monitor (H12_MON_* / H12_TRACE_* / H12_SUM_*): word offset and count of every field
+MON = dict(POS_VIOL_COUNT=(0, 12), POS_EXCESS_MAX=(12, 12), TAU_ABS_MAX=(24, 12), TAU_SAT_COUNT=(36, 12),
+           QD_ABS_MAX=(48, 12), QD_VIOL_COUNT=(60, 12), TAU_RATE_SUM=(72, 12), TAU_RATE_MAX=(84, 12),
+           Q_RATE_SUM=(96, 12), Q_RATE_MAX=(108, 12), TAU_PREV=(120, 12), Q_PREV=(132, 12), FORCE_MAX=(144, 2),
+           FORCE_SUM=(146, 2), FORCE_VIOL_COUNT=(148, 2), SUBSTEPS=(150, 1), CONTACT_SUBSTEPS=(151, 1),
+           FORCE_PAIR_SUM=(152, 1), FORCE_PAIR_MAX=(153, 1))
+MON_WORDS = 154
+MON_COUNTS = ("POS_VIOL_COUNT", "TAU_SAT_COUNT", "QD_VIOL_COUNT", "FORCE_VIOL_COUNT", "SUBSTEPS", "CONTACT_SUBSTEPS")  # int32
+MON_SUMS = ("TAU_RATE_SUM", "Q_RATE_SUM", "FORCE_SUM", "FORCE_PAIR_SUM")
+MON_PREV = ("TAU_PREV", "Q_PREV")
+MON_LIMIT_QD, MON_LIMIT_FORCE, MON_LIMIT_WORDS = 0, 12, 13
+TRACE = dict(POS=(0, 3), QUAT=(3, 4), VLIN=(7, 3), WANG=(10, 3), Q=(13, 12), QD=(25, 12), TAU=(37, 12), FORCE=(49, 2))
+TRACE_WORDS = 51
+SUM_EXTRA = dict(ENVS_POS_VIOL=154, ENVS_FORCE_VIOL=155, ENVS_VEL_VIOL=156, ENVS_ANY_VIOL=157, ENVS=158)
+SUM_WORDS = 159
+
 # the Flat task's reward term names, in RewardManager order (kernel ids 0-11)
 REWARD_TERMS = [
     "track_lin_vel_xy_exp", "track_ang_vel_z_exp", "ang_vel_xy_l2", "dof_torques_l2", "dof_acc_l2",
@@ -274,6 +290,14 @@ def load_library(path: str | os.PathLike | None = None):
     lib.h12env_set_terrain.restype = C.c_int
     lib.h12env_step_physics.argtypes = [vp, vp, C.c_int, vp]
     lib.h12env_step_physics.restype = C.c_int
+    if hasattr(lib, "h12env_monitor_layout"):  # (an older library, loaded as an A/B baseline, lacks the monitor)
+        szp = C.POINTER(C.c_size_t)
+        lib.h12env_monitor_layout.argtypes = [C.c_int, C.c_int, C.c_int, szp, szp, szp]
+        lib.h12env_monitor_layout.restype = C.c_int
+        lib.h12env_step_physics_monitored.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]
+        lib.h12env_step_physics_monitored.restype = C.c_int
+        lib.h12env_monitor_reduce.argtypes = [vp, vp, vp, vp]
+        lib.h12env_monitor_reduce.restype = C.c_int
     lib.h12env_rollout_layout.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.h12env_rollout_layout.restype = C.c_int
     lib.h12env_rollout_decode.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
@@ -338,4 +362,5 @@ EXPORTED_SYMBOLS = [
     "h12env_set_reward_weights", "h12env_set_constraint_max_p", "h12env_eval_terms", "h12env_eval_self_contacts",
     "h12env_rollout_layout", "h12env_rollout_decode", "h12env_fence_create", "h12env_fence_destroy",
     "h12env_fence_signal", "h12env_fence_wait", "h12env_step_lds", "h12env_check",
+    "h12env_monitor_layout", "h12env_step_physics_monitored", "h12env_monitor_reduce",
 ]

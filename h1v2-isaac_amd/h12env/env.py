@@ -603,9 +603,14 @@ class H12VelocityEnv:
             self.reset_buf = self.reset_terminated
             self._rollout = None
 
-    def step_physics(self, q_ref: torch.Tensor, n_substeps: int):
-        """Parity hook: physics only, PD towards a held joint target (h12env_step_physics)."""
+    def step_physics(self, q_ref: torch.Tensor, n_substeps: int, monitor=None):
+        """Parity hook: physics only, PD towards a held joint target (h12env_step_physics).  With monitor (a
+        h12env.safety.SafetyMonitor of this env) the same substeps run through h12env_step_physics_monitored, which
+        leaves the same state and records every substep into the monitor."""
         q = q_ref.to(device=self.device, dtype=torch.float32).contiguous()
+        if monitor is not None:
+            monitor._step(self, q, int(n_substeps))
+            return
         check(self._lib, self._lib.h12env_step_physics(self._h, C.c_void_p(q.data_ptr()), int(n_substeps),
                                                        self._stream()), "h12env_step_physics")
 

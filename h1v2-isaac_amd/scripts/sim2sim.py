@@ -4,7 +4,7 @@ MuJoCo-mode physics (1 kHz PD x control_dt/0.001 substeps, MJCF torque clamps) f
 deploy stack's observation / action handling (h12env.export.DeployController) -- the loop of the
 reference's scripts/deploy/sim2sim.py (RLPolicy.step -> H12Mujoco.step), which runs one env in MuJoCo.
 
-    python sim2sim.py <policy_dir> [--num_envs 64] [--episode_length 5] [--command 0.5 0 0] [--log_dir out]
+    python sim2sim.py <policy_dir> [--num_envs 64] [--episode_length 5] [--command 0.5 0 0] [--log_dir out] [--safety]
 
 policy_dir holds policy.pt and env.yaml (what play.py exports).  Commands are in the deploy convention
 ([-1, 1] per axis, scaled into env.yaml's command_ranges).  --log_dir writes env 0's trajectory in the
@@ -30,6 +30,8 @@ def main(argv=None) -> int:
     ap.add_argument("--log_dir", type=Path, default=None)
     ap.add_argument("--fused", action="store_true",
                     help="run policy.pt's actor and normaliser as one fused HIP launch (h12env.policy.FusedMLP)")
+    ap.add_argument("--safety", action="store_true",
+                    help="run the on-device safety monitor over all envs and print its summary (h12env.safety)")
     args = ap.parse_args(argv)
 
     import torch
@@ -57,15 +59,24 @@ def main(argv=None) -> int:
     log = TrajectoryLogger(env, 0) if args.log_dir else None
     if log:
         log.record_limits()
+    mon = None
+    if args.safety:
+        from h12env.safety import SafetyMonitor
+
+        mon = SafetyMonitor(env)
     steps = int(round(args.episode_length / pcfg["control_dt"]))
     for k in range(steps):
         q_ref = ctrl(env_state(env), cmd)
-        env.step_physics(q_ref, cfg.decimation)
+        env.step_physics(q_ref, cfg.decimation, monitor=mon)
         if log:
             log.record_metrics((k + 1) * pcfg["control_dt"])
     z = env._field("POS")[2]
     print(f"[sim2sim] {args.num_envs} envs x {steps} control steps; base height mean {z.mean().item():.3f} m "
           f"(min {z.min().item():.3f})")
+    if mon:
+        from eval_policy import format_tables
+
+        print(format_tables(mon.summary()))
     if log:
         print(f"[sim2sim] trajectory of env 0: {log.save_data(args.log_dir)}")
     env.close()

@@ -366,6 +366,65 @@ int h12env_set_terrain(h12env* h, const float* heights, int nx, int ny, float hs
 /* Parity hook: n_substeps physics steps with a held joint target q_ref (N x 12) using the
  * configured mode (PD, limits, contact), no MDP.  Mirrors H12Mujoco.step. */
 int h12env_step_physics(h12env* h, const float* q_ref, int n_substeps, void* stream);
+
+/* ---- Safety monitor of the physics-only path (additive to ABI 9).  Replaces the per-substep log and its checkers of the
+ * deploy workflow (packages/biped_deploy/biped_deploy/utils/mj_logger.py, eval/safety_checker.py, eval/eval_policy.py)
+ * with accumulators kept on the device for every env.
+ * Monitor buffer: caller-owned, 32-bit words, field-major [H12_MON_WORDS][n] like the workspace (word w of env i at
+ * w * n + i).  Counts are int32, everything else fp32.  Per-joint fields hold 12 words in MJCF joint order with real
+ * (not mirrored) signs, per-foot fields 2 words (left, right).  Zero the buffer (or an env's column) to reset it: an env
+ * whose H12_MON_SUBSTEPS is 0 records rate 0 on its next substep. */
+enum {
+  H12_MON_POS_VIOL_COUNT = 0,   /* 12 i32  substeps with q outside [q_lower, q_upper] (a q on a limit is inside) */
+  H12_MON_POS_EXCESS_MAX = 12,  /* 12 f32  max over substeps of max(q_lower - q, q - q_upper, 0) */
+  H12_MON_TAU_ABS_MAX = 24,     /* 12 f32  max |applied torque| */
+  H12_MON_TAU_SAT_COUNT = 36,   /* 12 i32  substeps with |applied torque| at the clamp */
+  H12_MON_QD_ABS_MAX = 48,      /* 12 f32  max |qd| */
+  H12_MON_QD_VIOL_COUNT = 60,   /* 12 i32  substeps with |qd| > the caller's velocity limit (limit 0: not counted) */
+  H12_MON_TAU_RATE_SUM = 72,    /* 12 f32  sum of |tau_k - tau_{k-1}| (MJLogger action_rate), one add per substep */
+  H12_MON_TAU_RATE_MAX = 84,    /* 12 f32 */
+  H12_MON_Q_RATE_SUM = 96,      /* 12 f32  sum of |q_k - q_{k-1}| (MJLogger joint_pos_rate) */
+  H12_MON_Q_RATE_MAX = 108,     /* 12 f32 */
+  H12_MON_TAU_PREV = 120,       /* 12 f32  torque of the last record */
+  H12_MON_Q_PREV = 132,         /* 12 f32  position of the last record */
+  H12_MON_FORCE_MAX = 144,      /*  2 f32  max foot contact-force norm */
+  H12_MON_FORCE_SUM = 146,      /*  2 f32  its sum over the substeps */
+  H12_MON_FORCE_VIOL_COUNT = 148, /* 2 i32 substeps with the norm > the caller's force limit */
+  H12_MON_SUBSTEPS = 150,       /*  1 i32  records taken */
+  H12_MON_CONTACT_SUBSTEPS = 151, /* 1 i32 substeps where either foot force != 0 (eval_policy.extract_contact_force) */
+  H12_MON_FORCE_PAIR_SUM = 152, /*  1 f32  sum of left + right over those substeps */
+  H12_MON_FORCE_PAIR_MAX = 153, /*  1 f32  max of left + right */
+  H12_MON_WORDS = 154
+};
+/* Limits passed to the monitored step (device, H12_MON_LIMIT_WORDS floats): per-joint |qd| limit, then the foot force
+ * limit (MJLogger.record_limits: total mass x g). */
+enum { H12_MON_LIMIT_QD = 0, H12_MON_LIMIT_FORCE = 12, H12_MON_LIMIT_WORDS = 13 };
+/* Trace record of one env-substep (fp32 words): the state before the substep, the clamped torque applied in it and the
+ * foot contact-force norms it reports (|net force on the foot|, mean over the inner steps, as the contact sensor). */
+enum {
+  H12_TRACE_POS = 0, H12_TRACE_QUAT = 3, H12_TRACE_VLIN = 7, H12_TRACE_WANG = 10, H12_TRACE_Q = 13, H12_TRACE_QD = 25,
+  H12_TRACE_TAU = 37, H12_TRACE_FORCE = 49, H12_TRACE_WORDS = 51
+};
+/* Summary record written by h12env_monitor_reduce: H12_SUM_WORDS 8-byte words.  Word w < H12_MON_WORDS folds monitor
+ * word w over the envs: counts -> int64 sum, maxima -> double maximum, sums -> double sum in env order (blocked, fixed);
+ * the two "previous record" fields -> 0.  Then the number of envs with any position / force / velocity violation, with
+ * any of the three, and the env count (int64). */
+enum {
+  H12_SUM_ENVS_POS_VIOL = H12_MON_WORDS, H12_SUM_ENVS_FORCE_VIOL, H12_SUM_ENVS_VEL_VIOL, H12_SUM_ENVS_ANY_VIOL,
+  H12_SUM_ENVS, H12_SUM_WORDS
+};
+/* Buffer sizes for n_envs envs, n_trace traced envs and n_substeps substeps per call (no handle, no device needed).
+ * summary_bytes covers the summary record followed by the reduce kernel's partial records (caller-owned scratch). */
+int h12env_monitor_layout(int n_envs, int n_trace, int n_substeps, size_t* monitor_bytes, size_t* trace_bytes,
+                          size_t* summary_bytes);
+/* h12env_step_physics with the monitor: leaves the workspace bit-identical to h12env_step_physics and accumulates every
+ * substep's record into monitor (required); limits (required) as above; trace (may be NULL with n_trace = 0):
+ * [n_substeps][n_trace][H12_TRACE_WORDS] records of envs [trace_env0, trace_env0 + n_trace). */
+int h12env_step_physics_monitored(h12env* h, const float* q_ref, int n_substeps, void* monitor, const float* limits,
+                                  float* trace, int trace_env0, int n_trace, void* stream);
+/* Fold the monitor over the envs into summary (h12env_monitor_layout's summary_bytes; two launches, deterministic). */
+int h12env_monitor_reduce(h12env* h, const void* monitor, void* summary, void* stream);
+
 /* Parity hook: the MDP term code of h12env_step (unweighted reward terms [H12_NREW][N], terminated, truncated
  * and, on a CaT env, the constraint rows [H12_NCSTR_COLS + 4][N] into cstr: the 56 raw columns, the no_move flag,
  * the pre-reset episode length, and foot_clearance's updated swing height (left, right)) evaluated on the workspace state as

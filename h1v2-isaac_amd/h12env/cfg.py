@@ -22,6 +22,7 @@ from dataclasses import dataclass, field, replace
 from ._abi import (ABI_VERSION, CONSTRAINT_TERMS, MODE_ISAACLAB, MODE_MUJOCO, NCSTR, NHIST, NJ, NREW, REWARD_FUNCS,
                    REWARD_TERMS, TASK_FLAT, TASK_ROUGH, H12Config)
 from .model import DEFAULT_JOINT_POS
+from .render import ViewerCfg
 
 
 @dataclass
@@ -499,6 +500,7 @@ class H12FlatEnvCfg:
     curriculum: CurriculumCfg = field(default_factory=CurriculumCfg)
     constraints: "ConstraintsCfg | None" = None   # the CaT task's ConstraintManager terms
     fix_base: bool = False
+    viewer: ViewerCfg = field(default_factory=ViewerCfg)  # env.render() / RecordVideo camera (h12env.render)
 
     @property
     def task(self) -> int:

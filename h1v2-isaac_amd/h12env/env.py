@@ -260,12 +260,15 @@ class H12VelocityEnv:
     """Drop-in for ``ManagerBasedRLEnv`` on ``Isaac-Velocity-Flat-H12_12dof-v0``."""
 
     is_vector_env = True
-    metadata = {"render_modes": [None], "isaac_sim_version": "none (MI355X-native)"}
+    metadata = {"render_modes": [None, "rgb_array"], "isaac_sim_version": "none (MI355X-native)"}
 
     def __init__(self, cfg: H12FlatEnvCfg | None = None, render_mode: str | None = None, env_offset: int = 0,
                  obs_copy: bool = False, **kwargs):
         self.cfg = cfg if cfg is not None else H12FlatEnvCfg()
+        if render_mode not in self.metadata["render_modes"]:
+            raise ValueError(f"render_mode {render_mode!r} is not one of {self.metadata['render_modes']}")
         self.render_mode = render_mode
+        self._renderer = None  # h12env.render.Renderer, created by the first render()
         self.device = torch.device(self.cfg.sim.device)
         if self.device.type != "cuda":
             raise RuntimeError(f"H12VelocityEnv runs on the MI355X HIP path only (device={self.device})")
@@ -673,7 +676,15 @@ class H12VelocityEnv:
         self.common_step_counter = snap["counter"]
 
     def render(self, recompute: bool = False):
-        return None
+        """render_mode="rgb_array": the (H, W, 3) uint8 frame of cfg.viewer.env_index from the device ray-caster
+        (h12env.render); None for render_mode=None."""
+        if self.render_mode != "rgb_array":
+            return None
+        if self._renderer is None:
+            from .render import Renderer
+
+            self._renderer = Renderer(self)
+        return self._renderer.render()[0].cpu().numpy()
 
     def _flush_log(self):
         if not self._closed:

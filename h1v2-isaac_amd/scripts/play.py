@@ -30,6 +30,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true",
                     help="run the policy as one fused HIP launch (h12env.policy.FusedMLP) instead of torch modules")
+    ap.add_argument("--video", action="store_true", default=False, help="Record a video of the rollout.")
+    ap.add_argument("--video_length", type=int, default=200, help="Length of the recorded video (in steps).")
     args = ap.parse_args(argv)
 
     import gymnasium as gym
@@ -50,7 +52,13 @@ def main(argv=None) -> int:
     root = os.path.abspath(os.path.join("logs", "rsl_rl", args.experiment_name or agent_cfg.experiment_name))
     path = get_checkpoint_path(root, args.load_run, args.checkpoint)
     print(f"[INFO]: Loading model checkpoint from: {path}")
-    env = RslRlVecEnvWrapper(gym.make(args.task, cfg=env_cfg))
+    env = gym.make(args.task, cfg=env_cfg, render_mode="rgb_array" if args.video else None)
+    if args.video:  # the reference's play.py: one video from step 0 under <run>/videos/play
+        vk = {"video_folder": os.path.join(os.path.dirname(path), "videos", "play"),
+              "step_trigger": lambda step: step == 0, "video_length": args.video_length, "disable_logger": True}
+        print("[INFO] Recording videos during training.")
+        env = gym.wrappers.RecordVideo(env, **vk)
+    env = RslRlVecEnvWrapper(env)
     runner = OnPolicyRunner(env, agent_cfg.to_dict(), log_dir=None, device=args.device)
     runner.load(path)
     policy = runner.get_inference_policy(device=args.device, fused=args.fused)
@@ -64,8 +72,10 @@ def main(argv=None) -> int:
     print(f"[INFO]: exported to {out}")
     obs, _ = env.get_observations()
     with torch.inference_mode():
-        for _ in range(args.steps):
+        for timestep in range(1, args.steps + 1):
             obs, _, _, _ = env.step(policy(obs))
+            if args.video and timestep == args.video_length:  # exit the play loop after recording one video
+                break
     env.close()
     return 0
 

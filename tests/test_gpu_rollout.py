@@ -8,7 +8,8 @@
   slots of the returned rows, and the reward / done tensors the step returned are the records themselves;
 * two ranks of bench.py's N > 1 path (child processes, both on cuda:0, gloo: RCCL refuses two ranks on one device):
   the line carries the c4_rollout_allgather split, and the decoded rows and gathered records equal one process
-  stepping all 2N envs with the same actions, bit for bit."""
+  stepping all 2N envs with the same actions, bit for bit.
+The rebuild on planted records (every window path, chosen done patterns): tests/test_gpu_rollout_decode.py."""
 import json
 import os
 import socket

@@ -5523,7 +5523,7 @@ int h12env_set_terrain(h12env* hh, const float* heights, int nx, int ny, float h
   if (!h) return set_err(H12_E_ARG, "null handle");
   if (!heights || nx < 2 || ny < 2 || !(hscale > 0)) return set_err(H12_E_ARG, "heights (nx, ny >= 2, hscale > 0) required");
   if ((origins == nullptr) != (rows <= 0 || cols <= 0) || rows > 0xFFFF || cols > 0x7FFF)
-    return set_err(H12_E_ARG, "origins need rows, cols in 1..32767");
+    return set_err(H12_E_ARG, "origins need rows in 1..65535 and cols in 1..32767");
   if (h->P.curriculum && !origins) return set_err(H12_E_ARG, "the terrain curriculum needs the origins table");
   h->P.t_h = heights;
   h->P.t_nx = nx;

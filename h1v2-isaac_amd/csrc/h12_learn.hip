@@ -2,6 +2,7 @@
 //
 //   h12learn_rms_forward  running mean/variance update fused with the normalisation (RunningMeanStd.forward)
 //   h12learn_gae_soft     GAE over soft (probabilistic) terminations
+//   h12learn_mirror_rows  minibatch gather + mirror-symmetry column map + concatenation (h12env/symmetry.py)
 //
 // rms_forward, update != 0, is two launches:
 //   1. rms_stats_kernel   grid (row chunks, column tiles).  A block reduces RMS_ROWS rows x 64 columns: lanes run
@@ -37,6 +38,10 @@ constexpr int RMS_HEADER = 64;                      // bytes: the arrival counte
 constexpr int NORM_BLOCK = 256;
 constexpr int NORM_PER_THREAD = 4;
 constexpr int GAE_BLOCK = 64;
+constexpr int MIR_WAVES = 4;
+constexpr int MIR_WAVE_ROWS = 8;                     // rows a wave moves: 8 (16 with both) independent loads in flight
+constexpr int MIR_ROWS = MIR_WAVES * MIR_WAVE_ROWS;  // rows per block
+constexpr int MIR_COLS = 64;                         // one wave wide
 
 thread_local char g_learn_err[256] = "";
 int learn_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -262,6 +267,53 @@ __global__ __launch_bounds__(GAE_BLOCK) void gae_soft_kernel(const float* reward
   }
 }
 
+// Gather + mirror + concatenation.  Grid (row chunks, column tiles), as in rms_stats_kernel: lanes run along 64
+// output columns (dword accesses: a 450-float row is only 8-byte aligned), each of the 4 waves moves MIR_WAVE_ROWS
+// rows with the lane's table entry held in a register.  The map moves a column by a few places inside its term, so
+// a wave's reads of a row stay within the cache lines of its 64 columns and their neighbours; with both != 0 the
+// original and the mirrored read of a source row hit the same lines (one fetch of the row from HBM).  The data are
+// moved as 32-bit words and the sign is an XOR of bit 31: no floating-point instruction touches them, so NaN
+// payloads, infinities and -0.0 pass whatever the device code's fast-math flags are.  The row index is wave-uniform
+// (scalar loads of idx) and clamped to the source, the source column to the row.  A wave's rows past n re-read row
+// n - 1 and store nothing, so every load is unconditional and the 8 (16) loads of a lane are in flight together.
+template <bool BOTH, bool IDX>
+__global__ __launch_bounds__(MIR_WAVES * 64) void mirror_rows_kernel(const uint32_t* x, long long n_src_rows,
+                                                                     const long long* idx, long long n, int d,
+                                                                     const uint32_t* table, uint32_t* out) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c = blockIdx.y * MIR_COLS + lane;
+  const long long rbase = (long long)blockIdx.x * MIR_ROWS + (long long)w * MIR_WAVE_ROWS;
+  if (c >= d || rbase >= n) return;
+  const uint32_t t = table[c];
+  const uint32_t sign = t & 0x80000000u;
+  uint32_t src = t & 0x7fffffffu;
+  src = src < (uint32_t)d ? src : (uint32_t)d - 1u;
+  long long row[MIR_WAVE_ROWS];
+#pragma unroll
+  for (int i = 0; i < MIR_WAVE_ROWS; ++i) {  // the index loads first, so they are in flight together too
+    const long long r = rbase + i < n ? rbase + i : n - 1;
+    row[i] = IDX ? idx[r] : r;
+  }
+  uint32_t m[MIR_WAVE_ROWS], o[MIR_WAVE_ROWS];
+#pragma unroll
+  for (int i = 0; i < MIR_WAVE_ROWS; ++i) {
+    const long long k = row[i] < 0 ? 0 : (row[i] < n_src_rows ? row[i] : n_src_rows - 1);
+    const uint32_t* p = x + (size_t)k * (size_t)d;
+    m[i] = p[src];
+    if (BOTH) o[i] = p[c];
+  }
+  uint32_t* om = out + (BOTH ? (size_t)n * (size_t)d : (size_t)0);
+#pragma unroll
+  for (int i = 0; i < MIR_WAVE_ROWS; ++i) {
+    const long long r = rbase + i;
+    if (r < n) {
+      om[(size_t)r * (size_t)d + c] = m[i] ^ sign;
+      if (BOTH) out[(size_t)r * (size_t)d + c] = o[i];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -312,6 +364,39 @@ int h12learn_gae_soft(const float* rewards, const float* values, const float* do
   hipLaunchKernelGGL(gae_soft_kernel, dim3((N + GAE_BLOCK - 1) / GAE_BLOCK), dim3(GAE_BLOCK), 0, (hipStream_t)stream,
                      rewards, values, dones, true_dones, next_value, next_done, next_true_done, gamma, gamma_lambda, T,
                      N, advantages, returns);
+  LEARN_HIP_TRY(hipGetLastError());
+  return H12LEARN_OK;
+}
+
+int h12learn_mirror_rows(const float* x, long long n_src_rows, const long long* idx, long long n, int d,
+                         const int* table, int both, float* out, void* stream) {
+  if (!x) return learn_err(H12LEARN_E_ARG, "mirror_rows: x is null");
+  if (!table) return learn_err(H12LEARN_E_ARG, "mirror_rows: table is null");
+  if (!out) return learn_err(H12LEARN_E_ARG, "mirror_rows: out is null");
+  if (d < 1) return learn_err(H12LEARN_E_ARG, "mirror_rows: d = %d (must be >= 1)", d);
+  if (n < 0) return learn_err(H12LEARN_E_ARG, "mirror_rows: n = %lld (must be >= 0)", n);
+  if (n_src_rows < 1) return learn_err(H12LEARN_E_ARG, "mirror_rows: n_src_rows = %lld (must be >= 1)", n_src_rows);
+  if (!idx && n > n_src_rows)
+    return learn_err(H12LEARN_E_ARG, "mirror_rows: n = %lld rows of a source of n_src_rows = %lld without idx", n,
+                     n_src_rows);
+  if (n == 0) return H12LEARN_OK;
+  const long long chunks = (n + MIR_ROWS - 1) / MIR_ROWS;
+  const int tiles = (d + MIR_COLS - 1) / MIR_COLS;
+  if (chunks > 0x7fffffffLL || tiles > 65535)
+    return learn_err(H12LEARN_E_ARG, "mirror_rows: n = %lld, d = %d exceed the grid", n, d);
+  const dim3 grid((unsigned)chunks, (unsigned)tiles), block(MIR_WAVES * 64);
+  const uint32_t* xs = (const uint32_t*)x;
+  const uint32_t* tab = (const uint32_t*)table;
+  uint32_t* o = (uint32_t*)out;
+  hipStream_t s = (hipStream_t)stream;
+  if (both && idx)
+    hipLaunchKernelGGL((mirror_rows_kernel<true, true>), grid, block, 0, s, xs, n_src_rows, idx, n, d, tab, o);
+  else if (both)
+    hipLaunchKernelGGL((mirror_rows_kernel<true, false>), grid, block, 0, s, xs, n_src_rows, idx, n, d, tab, o);
+  else if (idx)
+    hipLaunchKernelGGL((mirror_rows_kernel<false, true>), grid, block, 0, s, xs, n_src_rows, idx, n, d, tab, o);
+  else
+    hipLaunchKernelGGL((mirror_rows_kernel<false, false>), grid, block, 0, s, xs, n_src_rows, idx, n, d, tab, o);
   LEARN_HIP_TRY(hipGetLastError());
   return H12LEARN_OK;
 }

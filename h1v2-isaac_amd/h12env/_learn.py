@@ -12,7 +12,7 @@ from ._abi import H12EnvError, load_library
 
 LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12learn_rms_forward",
                  "h12learn_gae_soft", "h12learn_mlp_max_width", "h12learn_mlp_packed_bytes", "h12learn_mlp_pack",
-                 "h12learn_mlp_forward", "h12learn_last_error"]
+                 "h12learn_mlp_forward", "h12learn_mirror_rows", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -60,6 +60,8 @@ def learn_library():
     lib.h12learn_mlp_pack.restype = C.c_int
     lib.h12learn_mlp_forward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.c_longlong, C.POINTER(C.c_void_p), vp]
     lib.h12learn_mlp_forward.restype = C.c_int
+    lib.h12learn_mirror_rows.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]
+    lib.h12learn_mirror_rows.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -133,6 +135,35 @@ def gae_soft(rewards, values, dones, true_dones, next_value, next_done, next_tru
                                       float(gamma), float(gamma) * float(gae_lambda), T, N, adv.data_ptr(),
                                       ret.data_ptr(), _stream(rewards.device)), "h12learn_gae_soft")
     return adv, ret
+
+
+def mirror_rows(x: torch.Tensor, table: torch.Tensor, idx: torch.Tensor | None = None, both: bool = False,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch: the rows ``idx`` (every row when None) of x [n_src][d] under the column map ``table`` (int32 [d],
+    src | flip << 31; h12env.symmetry.MirrorTable.packed).  ``both``: the 2n-row concatenation (gathered, mirrored)."""
+    lib = learn_library()
+    _f32(x, "x")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"mirror_rows: x {tuple(x.shape)} is not (n_src >= 1, d >= 1)")
+    n_src, d = x.shape
+    if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and table.shape == (d,)):
+        raise ValueError(f"mirror_rows: table must be a contiguous int32 CUDA tensor of {d} entries")
+    n = n_src
+    if idx is not None:
+        if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 1):
+            raise ValueError("mirror_rows: idx must be a contiguous 1-D int64 CUDA tensor")
+        n = idx.shape[0]
+    rows = 2 * n if both else n
+    if out is None:
+        out = torch.empty((rows, d), dtype=torch.float32, device=x.device)
+    elif _f32(out, "out").shape != (rows, d):
+        raise ValueError(f"mirror_rows: out must be ({rows}, {d})")
+    if n == 0:
+        return out
+    _check(lib, lib.h12learn_mirror_rows(x.data_ptr(), n_src, None if idx is None else idx.data_ptr(), n, d,
+                                         table.data_ptr(), int(bool(both)), out.data_ptr(), _stream(x.device)),
+           "h12learn_mirror_rows")
+    return out
 
 
 def mlp_max_width() -> int:

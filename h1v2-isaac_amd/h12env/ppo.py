@@ -11,7 +11,9 @@ Design for one process per MI355X:
     computes gradients on its 1/world share of each minibatch, and the gradients are averaged with one
     flat all-reduce -- so all ranks apply bit-identical updates (parameters are also broadcast from rank 0
     at start and on load);
-  * checkpoints use rsl_rl's layout ({"model_state_dict", "optimizer_state_dict", "iter", "infos"}).
+  * checkpoints use rsl_rl's layout ({"model_state_dict", "optimizer_state_dict", "iter", "infos"});
+  * rsl_rl's symmetry_cfg (mirror-image data augmentation, mirror loss) with the env's own mirror map
+    (h12env.symmetry): gather + mirror + concatenation of a minibatch are one launch inside the update graph.
 """
 from __future__ import annotations
 
@@ -325,7 +327,7 @@ class PPO:
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
-                 **kwargs):
+                 symmetry_cfg: dict | None = None, **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
@@ -356,6 +358,19 @@ class PPO:
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be fp32 or bf16, got {precision!r}")
         self.precision = precision
+        # rsl_rl 2.3 symmetry: mirror-image data augmentation and / or mirror loss; with both switches off the
+        # symmetry loss is computed for logging only.  None: the update is untouched.
+        self.symmetry = None
+        if symmetry_cfg is not None:
+            from .symmetry import resolve_func
+
+            s = dict(symmetry_cfg)
+            self.symmetry = {"use_data_augmentation": bool(s.get("use_data_augmentation", False)),
+                             "use_mirror_loss": bool(s.get("use_mirror_loss", False)),
+                             "mirror_loss_coeff": float(s.get("mirror_loss_coeff", 0.0)),
+                             "data_augmentation_func": resolve_func(s.get("data_augmentation_func")),
+                             "_env": s.get("_env")}
+        self._n_stats = 3 if self.symmetry is None else 4
 
     def init_storage(self, num_envs, num_steps, obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_steps, obs_shape[0],
@@ -500,9 +515,17 @@ class PPO:
         rate, clipped surrogate + clipped value loss, backward, (all-reduce), grad clip, Adam, statistics.
         Host-sync free on the fused path, so it is also the body of the captured HIP graph."""
         world = self.shard.world
-        obs = b["observations"][idx]
-        critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
-        actions = b["actions"][idx]
+        sym = self.symmetry
+        aug = sym is not None and sym["use_data_augmentation"]
+        n_orig = idx.shape[0]
+        if aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
+            obs, actions = self._augment(b["observations"], b["actions"], idx, "policy")
+            critic_obs = (self._augment(b["privileged_observations"], None, idx, "critic")[0]
+                          if "privileged_observations" in b else obs)
+        else:
+            obs = b["observations"][idx]
+            critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
+            actions = b["actions"][idx]
         target_values = b["values"][idx]
         advantages = b["advantages"][idx]
         returns = b["returns"][idx]
@@ -510,6 +533,9 @@ class PPO:
         old_mu, old_sigma = b["mu"][idx], b["sigma"][idx]
         if self.normalize_advantage_per_mini_batch:
             advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-8)
+        if aug:  # the mirrored samples keep their originals' statistics (normalised above on the original batch)
+            old_log_prob, target_values, advantages, returns = (torch.cat([t, t]) for t in
+                                                                (old_log_prob, target_values, advantages, returns))
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
                             enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
             self.policy.update_distribution(obs)  # rsl_rl calls act(); the sample itself is unused
@@ -519,6 +545,8 @@ class PPO:
                                               self.policy.distribution.stddev.float())
         log_prob = self.policy.get_actions_log_prob(actions)
         mu, sigma, entropy = self.policy.action_mean, self.policy.action_std, self.policy.entropy
+        if aug:  # the KL of the schedule and the entropy bonus are those of the original samples
+            mu, sigma, entropy = mu[:n_orig], sigma[:n_orig], entropy[:n_orig]
         if self.desired_kl is not None and self.schedule == "adaptive":
             with torch.no_grad():
                 kl = torch.sum(torch.log(sigma / old_sigma + 1e-5)
@@ -553,12 +581,45 @@ class PPO:
         else:
             value_loss = (returns - value).square().mean()
         loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+        if sym is not None:
+            symmetry_loss = self._symmetry_loss(obs, aug, n_orig)
+            if sym["use_mirror_loss"]:
+                loss = loss + sym["mirror_loss_coeff"] * symmetry_loss
         self.optimizer.zero_grad(set_to_none=True)  # backward writes the grads (no fill + add)
         loss.backward()
         self._allreduce_grads()
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         self.optimizer.step()
-        stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()])
+        if sym is not None:
+            stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach(),
+                                  symmetry_loss.detach()])
+        else:
+            stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()])
+
+    def _augment(self, obs, actions, idx, obs_type):
+        """data_augmentation_func on the rows ``idx``.  h12env.symmetry.augment takes the index itself: gather, mirror
+        and concatenation are then one h12learn_mirror_rows launch per tensor on the device."""
+        from . import symmetry as S
+
+        f, env = self.symmetry["data_augmentation_func"], self.symmetry["_env"]
+        if f is S.augment:
+            return f(obs=obs, actions=actions, env=env, obs_type=obs_type, idx=idx)
+        return f(obs=None if obs is None else obs[idx], actions=None if actions is None else actions[idx], env=env,
+                 obs_type=obs_type)
+
+    def _symmetry_loss(self, obs, aug: bool, n_orig: int):
+        """rsl_rl's mirror loss: the actor's mean on the mirrored observations against the mirror image of its mean
+        on the originals (the target carries no gradient).  Without use_mirror_loss it is a logged number only."""
+        sym = self.symmetry
+        f, env = sym["data_augmentation_func"], sym["_env"]
+        with torch.set_grad_enabled(sym["use_mirror_loss"] and torch.is_grad_enabled()):
+            if not aug:
+                obs = f(obs=obs, actions=None, env=env, obs_type="policy")[0]
+            with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
+                                enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
+                mean_all = self.policy.act_inference(obs.detach()).float()
+            target = f(obs=None, actions=mean_all[:n_orig], env=env, obs_type="policy")[1].detach()
+            return nn.functional.mse_loss(mean_all[n_orig:], target[n_orig:])
 
     def _graph_ok(self) -> bool:
         return (self._lr_t is not None and self.shard.world == 1 and str(self.device).startswith("cuda")
@@ -586,7 +647,7 @@ class PPO:
         update): the ~300 kernel launches of a minibatch cost one graph launch.  Warm-up runs on a side
         stream on the real parameters, which are restored bit-exactly before the capture."""
         self._g_idx = torch.zeros(mb, dtype=torch.long, device=self.device)
-        self._g_stats = torch.zeros(3, device=self.device)
+        self._g_stats = torch.zeros(self._n_stats, device=self.device)
         self.policy.distribution = None  # drop autograd graphs built on the default stream
         snap = self._snapshot()
         s = torch.cuda.Stream(device=self.device)
@@ -619,7 +680,7 @@ class PPO:
             stats = self._g_stats
             stats.zero_()
         else:
-            stats = torch.zeros(3, device=self.device)
+            stats = torch.zeros(self._n_stats, device=self.device)
         n_updates = 0
         for epoch in range(self.num_learning_epochs):
             # identical permutation on every rank (shared seed per epoch); each rank takes its share
@@ -640,8 +701,11 @@ class PPO:
         self.storage.clear()
         if self._lr_t is not None:
             self.learning_rate = float(self._lr_t)
-        v, sl, en = (stats / n_updates).tolist()
-        return {"value_function": v, "surrogate": sl, "entropy": en}
+        v, sl, en, *sy = (stats / n_updates).tolist()
+        out = {"value_function": v, "surrogate": sl, "entropy": en}
+        if sy:
+            out["symmetry"] = sy[0]
+        return out
 
     def optimizer_state_dict(self) -> dict:
         """The optimizer state with a plain-float learning rate (rsl_rl's checkpoint layout)."""
@@ -715,7 +779,8 @@ class OnPolicyRunner:
         policy = ActorCritic(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         self.alg_cfg.pop("class_name", None)
         self.alg_cfg.pop("rnd_cfg", None)
-        self.alg_cfg.pop("symmetry_cfg", None)
+        if self.alg_cfg.get("symmetry_cfg") is not None:  # rsl_rl hands the env to the augmentation function
+            self.alg_cfg["symmetry_cfg"] = {**self.alg_cfg["symmetry_cfg"], "_env": env}
         self.alg = PPO(policy, device=device, shard=self.shard, **self.alg_cfg)
         self.alg.broadcast_parameters()
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
@@ -815,7 +880,8 @@ class OnPolicyRunner:
         self.tot_time += it_time
         fps = int(steps / it_time) if it_time > 0 else 0
         scalars = {"Loss/value_function": loss["value_function"], "Loss/surrogate": loss["surrogate"],
-                   "Loss/entropy": loss["entropy"], "Loss/learning_rate": self.alg.learning_rate,
+                   "Loss/entropy": loss["entropy"], **({"Loss/symmetry": loss["symmetry"]} if "symmetry" in loss else {}),
+                   "Loss/learning_rate": self.alg.learning_rate,
                    "Policy/mean_noise_std": self.alg.policy.action_std.mean().item()
                    if self.alg.policy.distribution is not None else 0.0,
                    "Perf/total_fps": fps, "Perf/collection_time": collection_time, "Perf/learning_time": learn_time,

@@ -47,6 +47,11 @@ def build_parser() -> argparse.ArgumentParser:
     rl.add_argument("--checkpoint", type=str, default=None)
     rl.add_argument("--logger", type=str, default=None, choices={"wandb", "tensorboard", "neptune"})
     rl.add_argument("--log_project_name", type=str, default=None)
+    sym = ap.add_argument_group("symmetry", "rsl_rl's symmetry_cfg with the env's own mirror map (h12env.symmetry)")
+    sym.add_argument("--symmetry", type=str, default=None, choices=["augment", "mirror_loss", "both"],
+                     help="mirror-image data augmentation, the mirror loss, or both "
+                          "(fills agent.algorithm.symmetry_cfg; an agent.algorithm.symmetry_cfg=... override works too)")
+    sym.add_argument("--mirror_loss_coeff", type=float, default=None, help="weight of the mirror loss (default 1.0)")
     AppLauncher.add_app_launcher_args(ap)
     return ap
 
@@ -61,6 +66,22 @@ def apply_cli(agent_cfg, env_cfg, args):
             setattr(agent_cfg, attr, v)
     if agent_cfg.logger in {"wandb", "neptune"} and args.log_project_name:
         agent_cfg.wandb_project = agent_cfg.neptune_project = args.log_project_name
+    if getattr(args, "symmetry", None) is not None:
+        from isaaclab_rl.rsl_rl import RslRlSymmetryCfg
+
+        agent_cfg.algorithm.symmetry_cfg = RslRlSymmetryCfg(
+            use_data_augmentation=args.symmetry in ("augment", "both"),
+            use_mirror_loss=args.symmetry in ("mirror_loss", "both"),
+            mirror_loss_coeff=1.0 if args.mirror_loss_coeff is None else args.mirror_loss_coeff,
+            data_augmentation_func="h12env.symmetry:augment")
+    elif getattr(args, "mirror_loss_coeff", None) is not None:
+        if agent_cfg.algorithm.symmetry_cfg is None:
+            raise SystemExit("--mirror_loss_coeff needs --symmetry (or an agent.algorithm.symmetry_cfg override)")
+        s = agent_cfg.algorithm.symmetry_cfg
+        if isinstance(s, dict):
+            s["mirror_loss_coeff"] = args.mirror_loss_coeff
+        else:
+            s.mirror_loss_coeff = args.mirror_loss_coeff
     if args.num_envs is not None:
         env_cfg.scene.num_envs = args.num_envs
     env_cfg.seed = agent_cfg.seed

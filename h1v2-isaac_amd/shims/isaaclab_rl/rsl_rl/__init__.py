@@ -20,6 +20,17 @@ class RslRlPpoActorCriticCfg:
 
 
 @dataclass
+class RslRlSymmetryCfg:
+    """rsl_rl 2.3 symmetry options (isaaclab_rl.rsl_rl.symmetry_cfg.RslRlSymmetryCfg).  data_augmentation_func is
+    a callable or a "module:func" string with rsl_rl's signature (obs, actions, env, obs_type) -> (obs, actions);
+    the H1-2 tasks ship theirs as "h12env.symmetry:augment"."""
+    use_data_augmentation: bool = False
+    use_mirror_loss: bool = False
+    data_augmentation_func: object = None
+    mirror_loss_coeff: float = 0.0
+
+
+@dataclass
 class RslRlPpoAlgorithmCfg:
     class_name: str = "PPO"
     num_learning_epochs: int = 5
@@ -35,7 +46,7 @@ class RslRlPpoAlgorithmCfg:
     use_clipped_value_loss: bool = True
     clip_param: float = 0.2
     normalize_advantage_per_mini_batch: bool = False
-    symmetry_cfg: dict | None = None
+    symmetry_cfg: RslRlSymmetryCfg | dict | None = None
     rnd_cfg: dict | None = None
 
 
@@ -155,5 +166,5 @@ def export_policy_as_onnx(policy, normalizer, path: str, filename="policy.onnx",
     return f(policy, normalizer, path, filename, verbose)
 
 
-__all__ = ["RslRlOnPolicyRunnerCfg", "RslRlPpoActorCriticCfg", "RslRlPpoAlgorithmCfg", "RslRlVecEnvWrapper",
-           "export_policy_as_jit", "export_policy_as_onnx"]
+__all__ = ["RslRlOnPolicyRunnerCfg", "RslRlPpoActorCriticCfg", "RslRlPpoAlgorithmCfg", "RslRlSymmetryCfg",
+           "RslRlVecEnvWrapper", "export_policy_as_jit", "export_policy_as_onnx"]

@@ -2,7 +2,8 @@
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
- * further down, is the policy's forward itself (h12env/policy.py): normaliser and every layer in one launch.
+ * further down, is the policy's forward itself (h12env/policy.py): normaliser and every layer in one launch.  The
+ * rsl_rl-style PPO (h12env/ppo.py) uses h12learn_mirror_rows for its mirror-symmetry augmentation.
  *
  * Every compute entry point
  *   - takes raw device pointers and a HIP stream,
@@ -52,6 +53,18 @@ int h12learn_gae_soft(const float* rewards, const float* values, const float* do
                       const float* next_value, const float* next_done, const float* next_true_done,
                       float gamma, float gamma_lambda, int T, int N, float* advantages, float* returns,
                       void* stream);
+
+/* Mirror-symmetry map of observation / action rows (h12env/symmetry.py), fused with the minibatch gather and the
+ * concatenation of rsl_rl's data augmentation, in one launch:
+ *   out[r, j] = (flip[j] ? -x : x)[row(r), src[j]],  row(r) = idx ? idx[r] : r,  r < n, j < d.
+ * x is [n_src_rows][d], table[d] holds src | flip << 31, idx (null, or n int64 entries) selects the source rows.
+ * both != 0: out has 2n rows, rows [0, n) the gathered originals, rows [n, 2n) their mirrors (one read of each source
+ * row); both == 0: out has the n mirrored rows.  out must not overlap x.  The values move as 32-bit words and the sign
+ * is an XOR of bit 31, so NaN, +-inf and -0.0 pass bit for bit.  An idx entry outside [0, n_src_rows) is clamped into
+ * it and a src outside [0, d) to d - 1: nothing outside x is read.  Without idx, n <= n_src_rows.  n == 0 launches
+ * nothing. */
+int h12learn_mirror_rows(const float* x, long long n_src_rows, const long long* idx, long long n, int d,
+                         const int* table /* src | flip << 31 */, int both, float* out, void* stream);
 
 /* ---- fused policy MLP forward (csrc/h12_policy.hip): input normaliser + every Linear/ELU layer of up to
  * H12LEARN_MLP_MAX_NETS networks over one shared input, in one launch, in exact fp32 (f32-input MFMA). */

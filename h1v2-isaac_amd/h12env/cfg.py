@@ -223,8 +223,33 @@ class PolicyObsCfg:
 
 
 @dataclass
+class CriticObsCfg:
+    """The privileged observation group rsl_rl's asymmetric actor-critic reads as extras["observations"]["critic"]
+    (h12env.priv): one noise-free row per env, no history -- base_lin_vel, the policy's terms
+    without corruption (and, on a heightfield task, its height scan), base_height, feet_contact, feet_air_time,
+    feet_contact_time, feet_force, actuator_lag, sole_friction, added_mass.  The terms shared with the policy group
+    take its scales; `scales` holds those of the group's own terms (base_height ... added_mass): a missing one is
+    1, except feet_force, 1 / (total model mass x g) (h12env.priv.default_force_scale)."""
+    enable_corruption: bool = False
+    concatenate_terms: bool = True
+    history_length: int = 0
+    scales: dict = field(default_factory=dict)
+
+
+def enable_privileged_critic(env_cfg):
+    """The scripts' --privileged_critic: switch the env cfg's critic observation group on (defaults)."""
+    obs = getattr(env_cfg, "observations", None)
+    if obs is None or "critic" not in getattr(obs, "__dataclass_fields__", {}):
+        raise ValueError("--privileged_critic: this task's env cfg has no critic observation group")
+    if obs.critic is None:
+        obs.critic = CriticObsCfg()
+
+
+@dataclass
 class ObservationsCfg:
     policy: PolicyObsCfg = field(default_factory=PolicyObsCfg)
+    # None: no critic group (the critic reads the policy row); left out of the cfg dumps while it is None
+    critic: CriticObsCfg | None = field(default=None, metadata={"omit_if_none": True})
 
 
 @dataclass

@@ -9,6 +9,9 @@ in packages/biped_tasks/biped_tasks/utils/cat/cat_env.py:95-193):
   num_envs, device, step_dt, physics_dt, max_episode_length(_s), episode_length_buf (writable),
   cfg, observation_manager.group_obs_dim, action_manager.total_action_dim, unwrapped, close()
 
+With cfg.observations.critic set, the obs dicts also hold "critic": the privileged rows of h12env.priv (one more
+launch per step, behind the env's on the same stream).
+
 Every step is ONE launch of the fused HIP kernel in libh12env.so (no CPU fallback: a missing
 extension raises).  State lives in one device workspace owned by a torch uint8 tensor; fields are
 exposed as zero-copy torch views.
@@ -145,9 +148,15 @@ class _ObservationManager:
         if env.obs_dim == NOBS_ROUGH:
             terms = ["base_lin_vel"] + terms + ["height_scan"]
         self.active_terms = {"policy": terms}
+        if env._priv is not None:  # the privileged group (h12env.priv)
+            from .priv import term_names
+
+            self.group_obs_dim["critic"] = (env.critic_obs_dim,)
+            self.group_obs_concatenate["critic"] = True
+            self.active_terms["critic"] = term_names(env.terrain is not None)
 
     def compute(self):
-        return {"policy": self._env._obs[self._env._k]}
+        return self._env._groups(self._env._obs[self._env._k], False)
 
 
 class _RewardManager:
@@ -307,6 +316,7 @@ class H12VelocityEnv:
         self.extras: dict = {}
         self.terrain = None
         self._apply_startup()
+        self._init_critic()
         if self.terrain is not None:
             origins = self._field("ORIGIN").T  # moved in-kernel by the terrain curriculum
         else:
@@ -334,6 +344,37 @@ class H12VelocityEnv:
         self.scene.__dict__["robot"] = self.scene.articulations["robot"]
         self._configure_spaces()
         self._closed = False
+
+    def _init_critic(self):
+        """The privileged observation group (cfg.observations.critic, h12env.priv): its config struct and the two row
+        buffers, swapped with the policy's.  None when the group is off: step() then does nothing for it."""
+        self._priv = None
+        self.critic_obs_dim = None
+        if self.cfg.observations.critic is None:
+            return
+        from . import priv
+
+        lib = priv.priv_library()
+        pc = priv.priv_config(self)
+        self.critic_obs_dim = priv.W_TERRAIN if pc.terrain else priv.W_PLANE
+        self._crit = [torch.zeros(self.num_envs, self.critic_obs_dim, device=self.device) for _ in range(2)]
+        self._priv = (lib, pc, C.byref(pc), priv.check)
+
+    def _critic_rows(self):
+        """h12priv_observe of the workspace as it stands into the current critic buffer: one launch behind the env's
+        kernels on the same stream, no host sync."""
+        lib, _, ref, check_priv = self._priv
+        rc = lib.h12priv_observe(self._state.data_ptr(), self.num_envs, ref, self.foot_contact_force.data_ptr(),
+                                 self._crit[self._k].data_ptr(), _raw_stream(self._dev_index))
+        if rc:
+            check_priv(lib, rc, "h12priv_observe")
+
+    def _groups(self, policy, copy):
+        """The observation dict: the policy rows and, with the privileged group on, the current critic rows."""
+        if self._priv is None:
+            return {"policy": policy}
+        c = self._crit[self._k]
+        return {"policy": policy, "critic": c.clone() if copy else c}
 
     def _build_step_outs(self):
         """h12env_step output structs, one per observation buffer (their pointers never change), the log ring's
@@ -386,7 +427,7 @@ class H12VelocityEnv:
 
     @property
     def obs_buf(self):
-        return {"policy": self._obs[self._k]}
+        return self._groups(self._obs[self._k], False)
 
     def _field(self, name: str) -> torch.Tensor:
         off, cnt = FIELDS[name]
@@ -397,8 +438,10 @@ class H12VelocityEnv:
             import gymnasium as gym
             import numpy as np
 
-            self.single_observation_space = gym.spaces.Dict(
-                {"policy": gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,))})
+            groups = {"policy": gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,))}
+            if self._priv is not None:
+                groups["critic"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.critic_obs_dim,))
+            self.single_observation_space = gym.spaces.Dict(groups)
             self.single_action_space = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(NJ,))
             self.observation_space = gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
             self.action_space = gym.vector.utils.batch_space(self.single_action_space, self.num_envs)
@@ -407,6 +450,9 @@ class H12VelocityEnv:
             self.single_action_space = (NJ,)
             self.observation_space = {"policy": (self.num_envs, self.obs_dim)}
             self.action_space = (self.num_envs, NJ)
+            if self._priv is not None:
+                self.single_observation_space["critic"] = (self.critic_obs_dim,)
+                self.observation_space["critic"] = (self.num_envs, self.critic_obs_dim)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -512,7 +558,9 @@ class H12VelocityEnv:
         check(self._lib, self._lib.h12env_reset(self._h, None if mask is None else C.c_void_p(mask.data_ptr()),
                                                 C.c_void_p(obs.data_ptr()), self._stream()), "h12env_reset")
         self.extras = {}
-        return {"policy": obs.clone() if self.obs_copy else obs}, self.extras
+        if self._priv is not None:
+            self._critic_rows()
+        return self._groups(obs.clone() if self.obs_copy else obs, self.obs_copy), self.extras
 
     def step(self, action: torch.Tensor):
         a = action
@@ -565,9 +613,14 @@ class H12VelocityEnv:
         self._live_logs[self.common_step_counter] = weakref.ref(log)
         self.extras = {"log": log, "time_outs": self.reset_time_outs}
         obs_out = obs.clone() if self.obs_copy else obs
+        if self._priv is None:
+            obs_dict = {"policy": obs_out}
+        else:
+            self._critic_rows()
+            obs_dict = self._groups(obs_out, self.obs_copy)
         if self._cat:  # CaTEnv.step: dones = constraint termination probability, 1 where reset (cat_env.py:153-193)
-            return {"policy": obs_out}, self.reward_buf, self._dones, self.reset_time_outs, self.extras
-        return {"policy": obs_out}, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
+            return obs_dict, self.reward_buf, self._dones, self.reset_time_outs, self.extras
+        return obs_dict, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def bind_rollout(self, rec):
         """Record every following step into the compact rollout ``rec`` (h12env.rollout.RolloutRecorder; BASELINE
@@ -578,6 +631,8 @@ class H12VelocityEnv:
         the records) -- unbind, reset, and bind a fresh recorder."""
         if self.obs_dim == NOBS_ROUGH or self._cat:
             raise ValueError("bind_rollout needs the flat observation layout (history) and a non-CaT task")
+        if self._priv is not None:
+            raise ValueError("bind_rollout with a critic observation group: the compact records carry no critic row")
         if rec.n != self.num_envs or rec.history * 45 != self.obs_dim:
             raise ValueError("rollout recorder was built for another env shape")
         self._rollout_saved = (self.reward_buf, self.reset_terminated, self.reset_time_outs)
@@ -655,23 +710,33 @@ class H12VelocityEnv:
         check(self._lib, self._lib.h12env_observe(self._h, C.c_void_p(prev.data_ptr()), C.c_void_p(out.data_ptr()),
                                                   None if fm is None else C.c_void_p(fm.data_ptr()),
                                                   self._stream()), "h12env_observe")
-        return {"policy": out}
+        if self._priv is not None:
+            self._critic_rows()
+        return self._groups(out, False)
 
     def get_observations(self):
-        return {"policy": self._obs[self._k]}
+        return self._groups(self._obs[self._k], False)
 
     def snapshot(self) -> dict:
         """Device copy of everything step() reads (workspace, both observation buffers, step counter), so a
         window of steps can be replayed bit for bit with restore().  The library-internal carries of the
         deadzone command count and the CaT running maxima are not included (Flat / Rough tasks only)."""
-        return {"state": self._state.clone(), "obs": [o.clone() for o in self._obs], "k": self._k,
+        snap = {"state": self._state.clone(), "obs": [o.clone() for o in self._obs], "k": self._k,
                 "counter": self.common_step_counter}
+        if self._priv is not None:  # the critic rows and the foot forces the next reset() / observe() reads
+            snap["critic"] = [c.clone() for c in self._crit]
+            snap["foot_force"] = self.foot_contact_force.clone()
+        return snap
 
     def restore(self, snap: dict):
         self._flush_log()  # folds of steps before the restore land in their own slots first
         self._state.copy_(snap["state"])
         for o, s in zip(self._obs, snap["obs"]):
             o.copy_(s)
+        if self._priv is not None:
+            for c, s in zip(self._crit, snap["critic"]):
+                c.copy_(s)
+            self.foot_contact_force.copy_(snap["foot_force"])
         self._k = snap["k"]
         self.common_step_counter = snap["counter"]
 

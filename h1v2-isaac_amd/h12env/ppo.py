@@ -923,6 +923,12 @@ class OnPolicyRunner:
 
     def load(self, path: str, load_optimizer: bool = True):
         d = torch.load(path, map_location=self.device, weights_only=True)
+        w = d["model_state_dict"].get("critic.0.weight")
+        mine = self.alg.policy.critic[0].weight.shape[1]
+        if w is not None and w.shape[1] != mine:
+            raise ValueError(f"{path}: the checkpoint's critic reads {w.shape[1]}-wide observations, this env's "
+                             f"critic observation is {mine} wide -- the two were built with different "
+                             "--privileged_critic settings (env.observations.critic)")
         self.alg.policy.load_state_dict(d["model_state_dict"])
         if self.empirical_normalization and "obs_norm_state_dict" in d:
             self.obs_normalizer.load_state_dict(d["obs_norm_state_dict"])

@@ -12,6 +12,14 @@ term-major ([term][slot][component], oldest slot first), so the per-frame rule o
     joint_pos, joint_vel, actions                left_* <-> right_* by joint name; yaw and roll joints negated
     height_scan (17 x 11 rays, x fastest)        out[iy * 17 + ix] = in[(10 - iy) * 17 + ix]
 
+and, of the privileged ("critic") group (h12env.priv):
+
+    base_height, actuator_lag, added_mass        unchanged (the three actuator groups span both legs)
+    feet_contact, feet_air_time,
+    feet_contact_time, feet_force (left, right)  left <-> right
+    sole_friction (static L, dynamic L,
+                   static R, dynamic R)          the left sole's pair <-> the right sole's
+
 The joint rule is checked against the model's joint axes when a table is built (a rotation about z or x changes sign
 under the reflection, one about y does not).  The legs of the model are exact mirrors of each other; the base body
 is not, so the simulated robot has this symmetry only approximately.
@@ -37,6 +45,8 @@ SCAN_NX, SCAN_NY = 17, 11  # RayCasterCfg grid pattern 1.6 x 1.0 m at 0.1 m, x f
 _POLAR = ((0, False), (1, True), (2, False))   # (x, -y, z)
 _AXIAL = ((0, True), (1, False), (2, True))    # (-x, y, -z)
 _COMMAND = ((0, False), (1, True), (2, True))  # (vx, -vy, -wz)
+_SAME = {"base_height": 1, "actuator_lag": 3, "added_mass": 1}  # term -> width, components unchanged
+_FEET = ("feet_contact", "feet_air_time", "feet_contact_time", "feet_force")  # (left, right)
 
 
 class MirrorTable:
@@ -162,6 +172,12 @@ def _term_rule(term: str):
         return _joint_rule()
     if term == "height_scan":
         return [((SCAN_NY - 1 - iy) * SCAN_NX + ix, False) for iy in range(SCAN_NY) for ix in range(SCAN_NX)]
+    if term in _SAME:
+        return [(k, False) for k in range(_SAME[term])]
+    if term in _FEET:
+        return [(1, False), (0, False)]
+    if term == "sole_friction":  # H12_F_MU: [static L, dynamic L, static R, dynamic R] (h12env.startup)
+        return [(2, False), (3, False), (0, False), (1, False)]
     raise ValueError(f"no mirror rule for the observation term {term!r}")
 
 
@@ -197,6 +213,10 @@ def _cfg_terms(cfg, obs_type: str):
     group = getattr(cfg.observations, obs_type, None)
     if group is None:
         raise ValueError(f"the env cfg has no observation group {obs_type!r}")
+    if obs_type == "critic":  # the privileged row: its own term list, no history
+        from .priv import term_names
+
+        return term_names(cfg.scene.height_scanner is not None), group.history_length
     terms = ["base_ang_vel", "projected_gravity", "velocity_commands", "joint_pos", "joint_vel", "actions"]
     if getattr(group, "base_lin_vel", None) is not None:
         terms = ["base_lin_vel"] + terms

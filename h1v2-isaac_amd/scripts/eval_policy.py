@@ -81,6 +81,9 @@ def main(argv=None) -> int:
     ap.add_argument("--log_dir", type=Path, default=None)
     ap.add_argument("--fused", action="store_true",
                     help="run policy.pt's actor and normaliser as one fused HIP launch (h12env.policy.FusedMLP)")
+    ap.add_argument("--privileged_critic", action="store_true", default=False,
+                    help="build the env with the privileged critic observation group, as train.py / play.py do with "
+                         "this flag (the exported policy is the actor alone: the evaluation itself does not change)")
     args = ap.parse_args(argv)
     if not 0 <= args.trace_envs <= args.num_envs:
         ap.error("--trace_envs must be in 0..num_envs")
@@ -104,6 +107,10 @@ def main(argv=None) -> int:
     cfg.scene.num_envs = args.num_envs
     cfg.sim.device = args.device
     cfg.decimation = int(round(pcfg["control_dt"] / cfg.sim.dt))
+    if args.privileged_critic:
+        from h12env.cfg import enable_privileged_critic
+
+        enable_privileged_critic(cfg)
     env = H12VelocityEnv(cfg)
     env.reset()
     mon = SafetyMonitor(env, trace_envs=args.trace_envs)

@@ -30,6 +30,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true",
                     help="run the policy as one fused HIP launch (h12env.policy.FusedMLP) instead of torch modules")
+    ap.add_argument("--privileged_critic", action="store_true", default=False,
+                    help="the checkpoint was trained with train.py --privileged_critic (its critic reads the "
+                         "privileged observation group)")
     ap.add_argument("--video", action="store_true", default=False, help="Record a video of the rollout.")
     ap.add_argument("--video_length", type=int, default=200, help="Length of the recorded video (in steps).")
     args = ap.parse_args(argv)
@@ -48,6 +51,10 @@ def main(argv=None) -> int:
     agent_cfg = load_cfg_from_registry(args.task, "rsl_rl_cfg_entry_point")
     if args.num_envs:
         env_cfg.scene.num_envs = args.num_envs
+    if args.privileged_critic:
+        from h12env.cfg import enable_privileged_critic
+
+        enable_privileged_critic(env_cfg)
     env_cfg.sim.device = agent_cfg.device = args.device
     root = os.path.abspath(os.path.join("logs", "rsl_rl", args.experiment_name or agent_cfg.experiment_name))
     path = get_checkpoint_path(root, args.load_run, args.checkpoint)

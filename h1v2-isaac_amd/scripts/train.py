@@ -52,6 +52,9 @@ def build_parser() -> argparse.ArgumentParser:
                      help="mirror-image data augmentation, the mirror loss, or both "
                           "(fills agent.algorithm.symmetry_cfg; an agent.algorithm.symmetry_cfg=... override works too)")
     sym.add_argument("--mirror_loss_coeff", type=float, default=None, help="weight of the mirror loss (default 1.0)")
+    ap.add_argument("--privileged_critic", action="store_true", default=False,
+                    help="asymmetric actor-critic: the env also returns the noise-free privileged observation group "
+                         "\"critic\" (env.observations.critic = CriticObsCfg(), h12env.priv) and the critic reads it")
     AppLauncher.add_app_launcher_args(ap)
     return ap
 
@@ -82,6 +85,10 @@ def apply_cli(agent_cfg, env_cfg, args):
             s["mirror_loss_coeff"] = args.mirror_loss_coeff
         else:
             s.mirror_loss_coeff = args.mirror_loss_coeff
+    if getattr(args, "privileged_critic", False):
+        from h12env.cfg import enable_privileged_critic
+
+        enable_privileged_critic(env_cfg)
     if args.num_envs is not None:
         env_cfg.scene.num_envs = args.num_envs
     env_cfg.seed = agent_cfg.seed

@@ -10,7 +10,10 @@ def class_to_dict(obj):
     if dataclasses.is_dataclass(obj):
         out = {}
         for f in dataclasses.fields(obj):
-            out[f.name] = class_to_dict(getattr(obj, f.name))
+            v = getattr(obj, f.name)
+            if v is None and f.metadata.get("omit_if_none"):
+                continue  # an optional group that is off leaves the dump as it was before the field existed
+            out[f.name] = class_to_dict(v)
         return out
     if isinstance(obj, dict):
         return {k: class_to_dict(v) for k, v in obj.items()}

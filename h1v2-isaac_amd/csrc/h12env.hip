@@ -3160,9 +3160,13 @@ H12_DEV void obs_frame(const KParams& P, const EnvSt& s, int leg, int e, int n, 
       mtv(R, vcom, vb);
       for (int a = 0; a < 3; ++a) frame[(size_t)a * n + e] = vb[a];
       for (int a = 0; a < 3; ++a) frame[(size_t)(H12_ROUGH_FRAME + a) * n + e] = s.b.pos[a];
-      float hx = R[0][0], hy = R[1][0], hn = __builtin_amdgcn_rsqf(hx * hx + hy * hy);
-      frame[(size_t)(H12_ROUGH_FRAME + 3) * n + e] = hx * hn;
-      frame[(size_t)(H12_ROUGH_FRAME + 4) * n + e] = hy * hn;
+      // scan heading; (1, 0) for a vertical x axis, as in mdp_terms (a NaN heading sends every ray to the grid corner)
+      float hx = R[0][0], hy = R[1][0];
+      const float h2 = hx * hx + hy * hy;
+      const bool hv = h2 > 0.f;
+      const float hn = __builtin_amdgcn_rsqf(hv ? h2 : 1.f);
+      frame[(size_t)(H12_ROUGH_FRAME + 3) * n + e] = hv ? hx * hn : 1.f;
+      frame[(size_t)(H12_ROUGH_FRAME + 4) * n + e] = hv ? hy * hn : 0.f;
     }
     for (int a = 0; a < 3; ++a) frame[(size_t)(o + a) * n + e] = s.b.wang[a];
     for (int a = 0; a < 3; ++a) frame[(size_t)(o + 3 + a) * n + e] = -R[2][a];
@@ -3536,10 +3540,14 @@ H12_DEV void mdp_terms(const KParams& P, const EnvSt& s, int leg, const float R[
   mv(R, s.b.wang, ww);
   float vcom[3];
   base_com_vel<K>(P, s, R, vcom);
-  // yaw frame: heading direction of the body x axis in the world xy-plane
+  // yaw frame: heading direction of the body x axis in the world xy-plane; a vertical x axis (hx = hy = 0, where
+  // 0 * rsq(0) is not a number) has heading (1, 0), the reference's atan2(0, 0) = 0.  The rsq never sees the 0:
+  // device code is built with -ffinite-math-only, which may assume an infinity away
   float hx = R[0][0], hy = R[1][0];
-  float hn = __builtin_amdgcn_rsqf(hx * hx + hy * hy);
-  float cy = hx * hn, sy = hy * hn;
+  const float h2 = hx * hx + hy * hy;
+  const bool hv = h2 > 0.f;
+  float hn = __builtin_amdgcn_rsqf(hv ? h2 : 1.f);
+  float cy = hv ? hx * hn : 1.f, sy = hv ? hy * hn : 0.f;
   float vy0 = cy * vcom[0] + sy * vcom[1], vy1 = -sy * vcom[0] + cy * vcom[1];
   float ex = s.cmd[0] - vy0, ey = s.cmd[1] - vy1, ew = s.cmd[2] - ww[2];
   terms[H12_R_TRACK_LIN_VEL_XY] = __expf(-(ex * ex + ey * ey) * P.std2_inv);

@@ -1402,7 +1402,8 @@ static void obs_row_rough(const h12env_model* m, const h12env_config* c, const o
   for (int j = 0; j < NJ; ++j) v[k++] = e->p.q[j] - m->q_default[j];
   for (int j = 0; j < NJ; ++j) v[k++] = e->p.qd[j];
   for (int j = 0; j < NJ; ++j) v[k++] = e->act[j];
-  double hx = R[0][0], hy = R[1][0], hn = sqrt(hx * hx + hy * hy), cy = hx / hn, sy = hy / hn;
+  double hx = R[0][0], hy = R[1][0], hn = sqrt(hx * hx + hy * hy);
+  double cy = hn > 0 ? hx / hn : 1.0, sy = hn > 0 ? hy / hn : 0.0; /* vertical x axis: heading atan2(0, 0) = 0 */
   for (int iy = 0; iy < H12_SCAN_NY; ++iy)
     for (int ix = 0; ix < H12_SCAN_NX; ++ix) {
       double xl = c->scan_resolution * (ix - (H12_SCAN_NX - 1) / 2), yl = c->scan_resolution * (iy - (H12_SCAN_NY - 1) / 2);
@@ -1537,7 +1538,8 @@ int orc_mdp_terms(const h12env_model* m, const h12env_config* c, const orc_term_
   for (int f = 0; f < 2; ++f)
     for (int k = 4; k < 6; ++k) { /* ankle pitch, ankle roll */
       int j = 6 * f + k;
-      double mid = 0.5 * (m->q_lower[j] + m->q_upper[j]), half = 0.5 * (m->q_upper[j] - m->q_lower[j]) * c->soft_limit_factor;
+      double ql = m->q_lower[j], qu = m->q_upper[j]; /* promoted first: float - float would round the range to fp32 */
+      double mid = 0.5 * (ql + qu), half = 0.5 * (qu - ql) * c->soft_limit_factor;
       double lo_s = mid - half, hi_s = mid + half, q = in->p.q[j];
       s_lim += (q < lo_s ? lo_s - q : 0.0) + (q > hi_s ? q - hi_s : 0.0);
     }
@@ -1577,7 +1579,8 @@ int orc_mdp_terms(const h12env_model* m, const h12env_config* c, const orc_term_
       for (int k = 4; k < 6; ++k) s_da += fabs(in->p.q[6 * f + k] - m->q_default[6 * f + k]);
       for (int k = 0; k < 3; k += 2) { /* hip yaw, hip roll soft limits */
         int j = 6 * f + k;
-        double mid = 0.5 * (m->q_lower[j] + m->q_upper[j]), half = 0.5 * (m->q_upper[j] - m->q_lower[j]) * c->soft_limit_factor;
+        double ql = m->q_lower[j], qu = m->q_upper[j];
+        double mid = 0.5 * (ql + qu), half = 0.5 * (qu - ql) * c->soft_limit_factor;
         double lo_s = mid - half, hi_s = mid + half, q = in->p.q[j];
         s_lh += (q < lo_s ? lo_s - q : 0.0) + (q > hi_s ? q - hi_s : 0.0);
       }

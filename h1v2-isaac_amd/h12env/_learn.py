@@ -12,7 +12,10 @@ from ._abi import H12EnvError, load_library
 
 LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12learn_rms_forward",
                  "h12learn_gae_soft", "h12learn_mlp_max_width", "h12learn_mlp_packed_bytes", "h12learn_mlp_pack",
-                 "h12learn_mlp_forward", "h12learn_mirror_rows", "h12learn_last_error"]
+                 "h12learn_mlp_forward", "h12learn_mirror_rows", "h12learn_mlp_train_rows",
+                 "h12learn_mlp_train_max_width", "h12learn_mlp_packed_t_bytes", "h12learn_mlp_pack_t",
+                 "h12learn_mlp_forward_train", "h12learn_mlp_backward_workspace_bytes", "h12learn_mlp_backward",
+                 "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -62,6 +65,21 @@ def learn_library():
     lib.h12learn_mlp_forward.restype = C.c_int
     lib.h12learn_mirror_rows.argtypes = [vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]
     lib.h12learn_mirror_rows.restype = C.c_int
+    lib.h12learn_mlp_train_rows.argtypes = []
+    lib.h12learn_mlp_train_rows.restype = C.c_int
+    lib.h12learn_mlp_train_max_width.argtypes = []
+    lib.h12learn_mlp_train_max_width.restype = C.c_int
+    lib.h12learn_mlp_packed_t_bytes.argtypes = [C.POINTER(MlpDesc)]
+    lib.h12learn_mlp_packed_t_bytes.restype = C.c_size_t
+    lib.h12learn_mlp_pack_t.argtypes = [C.POINTER(MlpDesc), vp, vp]
+    lib.h12learn_mlp_pack_t.restype = C.c_int
+    lib.h12learn_mlp_forward_train.argtypes = [C.POINTER(MlpDesc), vp, vp, C.c_longlong, vp, C.POINTER(C.c_void_p), vp]
+    lib.h12learn_mlp_forward_train.restype = C.c_int
+    lib.h12learn_mlp_backward_workspace_bytes.argtypes = [C.POINTER(MlpDesc), C.c_longlong]
+    lib.h12learn_mlp_backward_workspace_bytes.restype = C.c_size_t
+    lib.h12learn_mlp_backward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.POINTER(C.c_void_p), C.c_longlong,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, C.c_size_t, vp]
+    lib.h12learn_mlp_backward.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -230,3 +248,79 @@ def mlp_forward(desc: MlpDesc, packed: torch.Tensor, x: torch.Tensor, out=None) 
     _check(lib, lib.h12learn_mlp_forward(C.byref(desc), packed.data_ptr(), x.data_ptr(), n, ys, _stream(x.device)),
            "h12learn_mlp_forward")
     return tuple(out)
+
+
+# ---- training side of the fused MLP (csrc/h12_policy_train.hip): one network, no normaliser
+def mlp_train_rows() -> int:
+    return learn_library().h12learn_mlp_train_rows()
+
+
+def mlp_train_max_width() -> int:
+    return learn_library().h12learn_mlp_train_max_width()
+
+
+def mlp_packed_t_bytes(desc: MlpDesc) -> int:
+    lib = learn_library()
+    nbytes = lib.h12learn_mlp_packed_t_bytes(C.byref(desc))
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_mlp_packed_t_bytes")
+    return nbytes
+
+
+def mlp_pack_t(desc: MlpDesc, packed_t: torch.Tensor):
+    """Packs the transposed weights of ``desc`` (the dgrad's operand) into ``packed_t``: one launch."""
+    lib = learn_library()
+    _f32(packed_t, "packed_t")
+    if packed_t.numel() * 4 < mlp_packed_t_bytes(desc):
+        raise ValueError("mlp_pack_t: packed_t is smaller than mlp_packed_t_bytes(desc)")
+    _check(lib, lib.h12learn_mlp_pack_t(C.byref(desc), packed_t.data_ptr(), _stream(packed_t.device)),
+           "h12learn_mlp_pack_t")
+
+
+def _widths(desc: MlpDesc) -> list[int]:
+    net = desc.nets[0]
+    return [net.dims[l] for l in range(net.n_layers + 1)]
+
+
+def mlp_forward_train(desc: MlpDesc, packed: torch.Tensor, x: torch.Tensor):
+    """One launch: (y [n][d_out], [h_l [n][dims[l+1]] for every hidden layer]) of the one network of ``desc``."""
+    lib = learn_library()
+    _f32(packed, "packed"), _f32(x, "x")
+    dims = _widths(desc)
+    if x.dim() != 2 or x.shape[1] != dims[0] or x.shape[0] < 1:
+        raise ValueError(f"mlp_forward_train: x {tuple(x.shape)} is not (n >= 1, {dims[0]})")
+    n = x.shape[0]
+    y = torch.empty((n, dims[-1]), dtype=torch.float32, device=x.device)
+    hs = [torch.empty((n, w), dtype=torch.float32, device=x.device) for w in dims[1:-1]]
+    hp = (C.c_void_p * max(1, len(hs)))(*[h.data_ptr() for h in hs])
+    _check(lib, lib.h12learn_mlp_forward_train(C.byref(desc), packed.data_ptr(), x.data_ptr(), n, y.data_ptr(), hp,
+                                               _stream(x.device)), "h12learn_mlp_forward_train")
+    return y, hs
+
+
+def mlp_backward(desc: MlpDesc, packed_t: torch.Tensor, dy: torch.Tensor, hs, need_dx: bool = False):
+    """Two launches: ([dZ_l for every hidden layer], [db_l for every layer], dX or None) from ``dy`` [n][d_out], the
+    activations ``hs`` saved by mlp_forward_train and the transposed pack."""
+    lib = learn_library()
+    _f32(packed_t, "packed_t"), _f32(dy, "dy")
+    dims = _widths(desc)
+    if dy.dim() != 2 or dy.shape[1] != dims[-1] or dy.shape[0] < 1:
+        raise ValueError(f"mlp_backward: dy {tuple(dy.shape)} is not (n >= 1, {dims[-1]})")
+    n, dev = dy.shape[0], dy.device
+    if len(hs) != len(dims) - 2:
+        raise ValueError(f"mlp_backward: {len(hs)} saved activations for {len(dims) - 2} hidden layers")
+    for l, h in enumerate(hs):
+        if _f32(h, f"hs[{l}]").shape != (n, dims[l + 1]):
+            raise ValueError(f"mlp_backward: hs[{l}] must be ({n}, {dims[l + 1]})")
+    dzs = [torch.empty((n, w), dtype=torch.float32, device=dev) for w in dims[1:-1]]
+    dbs = [torch.empty(w, dtype=torch.float32, device=dev) for w in dims[1:]]
+    dx = torch.empty((n, dims[0]), dtype=torch.float32, device=dev) if need_dx else None
+    nbytes = lib.h12learn_mlp_backward_workspace_bytes(C.byref(desc), n)
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_mlp_backward_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    arr = lambda ts: (C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])  # noqa: E731
+    _check(lib, lib.h12learn_mlp_backward(C.byref(desc), packed_t.data_ptr(), dy.data_ptr(), arr(hs), n, arr(dzs),
+                                          arr(dbs), None if dx is None else dx.data_ptr(), ws.data_ptr(), nbytes,
+                                          _stream(dev)), "h12learn_mlp_backward")
+    return dzs, dbs, dx

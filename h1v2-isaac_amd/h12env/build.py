@@ -26,7 +26,8 @@ def hipcc() -> str:
 
 
 def sources():
-    return [CSRC / "h12env.hip", CSRC / "h12_learn.hip", CSRC / "h12_policy.hip", CSRC / "h12_math.h", CSRC / "h12_model_gen.h",
+    return [CSRC / "h12env.hip", CSRC / "h12_learn.hip", CSRC / "h12_policy.hip", CSRC / "h12_policy_train.hip",
+            CSRC / "h12_math.h", CSRC / "h12_model_gen.h",
             REPO / "include" / "h12env.h", REPO / "include" / "h12learn.h", REPO / "include" / "h12render.h",
             REPO / "include" / "h12priv.h", CSRC / "h12_priv.hip", CSRC / "h12_render.hip"]
 
@@ -66,7 +67,8 @@ def build(force: bool = False, verbose: bool = True, extra_flags: list[str] | No
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Xarch_device",
            "-ffinite-math-only", "-Xarch_device", "-fno-signed-zeros", "-fPIC", "-shared", "-Wall",
            "-Wno-unused-function", "-o", str(OUT), str(CSRC / "h12env.hip"), str(CSRC / "h12_learn.hip"),
-           str(CSRC / "h12_policy.hip"), str(CSRC / "h12_priv.hip"), str(CSRC / "h12_render.hip")]
+           str(CSRC / "h12_policy.hip"), str(CSRC / "h12_policy_train.hip"), str(CSRC / "h12_priv.hip"),
+           str(CSRC / "h12_render.hip")]
     if extra_flags:
         cmd += extra_flags
     if verbose:

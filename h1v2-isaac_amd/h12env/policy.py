@@ -10,7 +10,10 @@ everywhere stays the torch path (``fused=False`` / ``--fused`` absent / ``H12_PO
 
 The packed copy of the weights is what the kernel reads: ``refresh()`` (one launch, capturable) re-packs it from the
 live parameters, so call it, or pass ``repack=True``, after the parameters changed.  No autograd.  On CPU tensors the
-torch modules are evaluated, so the surface is testable without a GPU; on CUDA a missing kernel is an error."""
+torch modules are evaluated, so the surface is testable without a GPU; on CUDA a missing kernel is an error.
+
+``TrainableFusedMLP`` (further down) is the learner's counterpart: one network with autograd, forward and backward on
+the training kernels of csrc/h12_policy_train.hip; ``FusedMLP`` itself stays forward only."""
 from __future__ import annotations
 
 import os
@@ -176,3 +179,106 @@ class FusedMLP:
         for p in actor.parameters():
             p.requires_grad_(False)
         return cls([actor], norm.to(device) if norm is not None else None)
+
+
+def learner_fused_enabled() -> bool:
+    """H12_LEARNER_FUSED=1: ppo.PPO routes the learning-phase actor and critic through TrainableFusedMLP."""
+    return os.environ.get("H12_LEARNER_FUSED", "0") == "1"
+
+
+def _wgrad(dz: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """dW = dZ^T H on the GEMM library, with ppo.SplitKLinear's rule: a 16-way split-K bmm for large batches."""
+    from .ppo import SplitKLinear
+
+    n, s = dz.shape[0], SplitKLinear.SPLIT_K
+    if n >= SplitKLinear.MIN_BATCH and n % s == 0:
+        return torch.bmm(dz.view(s, n // s, -1).transpose(1, 2), h.view(s, n // s, -1)).sum(0)
+    return dz.t() @ h
+
+
+class _FusedMLPFn(torch.autograd.Function):
+    """y = net(x) of one Linear/ELU network: pack W and W^T from the live parameters, h12learn_mlp_forward_train; the
+    backward is h12learn_mlp_backward (dgrad chain, ELU', bias gradients) and one library GEMM per weight gradient.
+    First derivatives only (once_differentiable).  CPU tensors: the same node over the torch operations."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        ctx.on_device = x.is_cuda
+        if not x.is_cuda:  # the torch modules' own operations, recorded here and differentiated once in backward
+            with torch.enable_grad():
+                xd = x.detach().requires_grad_(ctx.needs_input_grad[0])
+                ps = [p.detach().requires_grad_(ctx.needs_input_grad[1 + i]) for i, p in enumerate(params)]
+                h = xd
+                for i in range(0, len(ps), 2):
+                    h = nn.functional.linear(h, ps[i], ps[i + 1])
+                    if i + 2 < len(ps):
+                        h = nn.functional.elu(h)
+            ctx.torch_graph = (xd, ps, h)
+            return h.detach()
+        with torch.autocast(device_type="cuda", enabled=False):
+            pairs = [(params[i].detach(), params[i + 1].detach()) for i in range(0, len(params), 2)]
+            for w, b in pairs:
+                if not (w.is_cuda and w.device == x.device and b.device == x.device and w.dtype == torch.float32
+                        and b.dtype == torch.float32 and w.is_contiguous() and b.is_contiguous()):
+                    raise ValueError("TrainableFusedMLP: every parameter must be a contiguous float32 tensor on x's device")
+            xc = x.detach().float().contiguous()
+            desc = _learn.mlp_desc([pairs])
+            packed = torch.empty(_learn.mlp_packed_bytes(desc) // 4, dtype=torch.float32, device=x.device)
+            packed_t = torch.empty(_learn.mlp_packed_t_bytes(desc) // 4, dtype=torch.float32, device=x.device)
+            _learn.mlp_pack(desc, packed)
+            _learn.mlp_pack_t(desc, packed_t)
+            y, hs = _learn.mlp_forward_train(desc, packed, xc)
+            ctx.desc, ctx.x_dtype = desc, x.dtype
+            ctx.save_for_backward(xc, packed_t, *hs)
+            return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        if not ctx.on_device:
+            xd, ps, y = ctx.torch_graph
+            ctx.torch_graph = None
+            wanted = [t for t in [xd] + ps if t.requires_grad]
+            with torch.enable_grad():
+                got = iter(torch.autograd.grad(y, wanted, dy) if wanted else ())
+            return tuple(next(got) if t.requires_grad else None for t in [xd] + ps)
+        xc, packed_t, *hs = ctx.saved_tensors
+        with torch.autocast(device_type="cuda", enabled=False):
+            dy = dy.float().contiguous()
+            # the descriptor's shapes only: the backward reads the transposed pack and the saved activations
+            dzs, dbs, dx = _learn.mlp_backward(ctx.desc, packed_t, dy, hs, need_dx=ctx.needs_input_grad[0])
+            dzs = dzs + [dy]
+            acts = [xc] + list(hs)
+            grads = []
+            for l, (dz, db) in enumerate(zip(dzs, dbs)):
+                gw = _wgrad(dz, acts[l]) if ctx.needs_input_grad[1 + 2 * l] else None
+                grads += [gw, db if ctx.needs_input_grad[2 + 2 * l] else None]
+            return (None if dx is None else dx.to(ctx.x_dtype), *grads)
+
+
+class TrainableFusedMLP:
+    """``TrainableFusedMLP(net)(x)`` is ``net(x)`` with autograd, computed by the fused kernels: the forward and the
+    whole backward except the weight-gradient GEMMs are one HIP launch each (csrc/h12_policy_train.hip).  ``net``: an
+    ``nn.Sequential`` of nn.Linear / ELU(alpha=1) as for FusedMLP, every width at most ``mlp_train_max_width()``.  The
+    parameters are read live at every call (packed inside the autograd function, so also inside a captured graph).
+    First derivatives only: a double backward is refused.  On CPU tensors, or with grad disabled, the torch modules'
+    operations are evaluated (bit-identical to ``net``)."""
+
+    def __init__(self, net: nn.Module):
+        self.net = net
+        self._layers = _linears(net, 0)
+        if len(self._layers) > _learn.MLP_MAX_LAYERS:
+            raise ValueError(f"FusedMLP: network 0 has {len(self._layers)} linear layers (at most {_learn.MLP_MAX_LAYERS})")
+        max_width = _learn.mlp_train_max_width()
+        for lin in self._layers:
+            if max(lin.in_features, lin.out_features) > max_width or lin.weight.dtype != torch.float32:
+                raise ValueError(f"FusedMLP: network 0: {lin} is wider than {max_width} or not float32")
+        self.d_in = self._layers[0].in_features
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        if not torch.is_grad_enabled():
+            return self.net(x)
+        if x.is_cuda and (x.dim() != 2 or x.shape[1] != self.d_in or x.shape[0] < 1):
+            raise ValueError(f"TrainableFusedMLP: x {tuple(x.shape)} is not (n >= 1, {self.d_in})")
+        params = [p for lin in self._layers for p in (lin.weight, lin.bias)]
+        return _FusedMLPFn.apply(x, *params)

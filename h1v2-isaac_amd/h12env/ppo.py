@@ -132,14 +132,29 @@ class ActorCritic(nn.Module):
         else:
             raise ValueError(f"unknown noise_std_type {noise_std_type!r}")
         self.distribution: Normal | None = None
+        self._fused_learner: dict | None = None
         Normal.set_default_validate_args(False)
+
+    def enable_fused_learner(self):
+        """Route actor and critic through h12env.policy.TrainableFusedMLP (fused HIP forward and backward) whenever
+        grad is enabled on CUDA tensors.  Same parameters, same state dict.  ValueError when a network is not
+        Linear/ELU or is wider than the training kernels support."""
+        from .policy import TrainableFusedMLP
+
+        self._fused_learner = {"actor": TrainableFusedMLP(self.actor), "critic": TrainableFusedMLP(self.critic)}
+
+    def _net(self, name: str, obs):
+        f = self.__dict__.get("_fused_learner")
+        if f is not None and obs.is_cuda and torch.is_grad_enabled():
+            return f[name](obs)
+        return getattr(self, name)(obs)
 
     def _std(self, mean):
         s = self.std if self.noise_std_type == "scalar" else torch.exp(self.log_std)
         return s.expand_as(mean)
 
     def update_distribution(self, obs):
-        mean = self.actor(obs)
+        mean = self._net("actor", obs)
         self.distribution = Normal(mean, self._std(mean))
 
     def act(self, obs, **kw):
@@ -147,10 +162,10 @@ class ActorCritic(nn.Module):
         return self.distribution.sample()
 
     def act_inference(self, obs):
-        return self.actor(obs)
+        return self._net("actor", obs)
 
     def evaluate(self, critic_obs, **kw):
-        return self.critic(critic_obs)
+        return self._net("critic", critic_obs)
 
     def get_actions_log_prob(self, actions):
         return self.distribution.log_prob(actions).sum(dim=-1)
@@ -327,7 +342,7 @@ class PPO:
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
-                 symmetry_cfg: dict | None = None, **kwargs):
+                 symmetry_cfg: dict | None = None, fused_learner: bool | None = None, **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
@@ -358,6 +373,24 @@ class PPO:
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be fp32 or bf16, got {precision!r}")
         self.precision = precision
+        # opt-in: the update's actor and critic on the fused HIP forward / backward (h12env.policy.TrainableFusedMLP,
+        # DESIGN 7l).  None reads H12_LEARNER_FUSED=1.  The collection (_act_body) is untouched; on CPU the torch
+        # modules run.  The default stays the torch path.
+        if fused_learner is None:
+            from .policy import learner_fused_enabled
+
+            fused_learner = learner_fused_enabled()
+        self.fused_learner = bool(fused_learner)
+        if self.fused_learner:
+            if precision == "bf16":
+                raise ValueError("fused_learner: the fused kernels are exact fp32, precision='bf16' is not supported")
+            if not hasattr(self.policy, "enable_fused_learner"):
+                raise ValueError(f"fused_learner: {type(self.policy).__name__} has no enable_fused_learner()")
+            try:
+                self.policy.enable_fused_learner()
+            except ValueError as e:
+                raise ValueError(f"fused_learner: the policy's networks cannot run on the fused kernels "
+                                 f"(Linear/ELU only, every width at most the kernels' maximum): {e}") from e
         # rsl_rl 2.3 symmetry: mirror-image data augmentation and / or mirror loss; with both switches off the
         # symmetry loss is computed for logging only.  None: the update is untouched.
         self.symmetry = None

@@ -55,6 +55,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="asymmetric actor-critic: the env also returns the noise-free privileged observation group "
                          "\"critic\" (env.observations.critic = CriticObsCfg(), h12env.priv) and the critic reads it")
+    ap.add_argument("--fused_learner", action="store_true", default=False,
+                    help="the PPO update's actor and critic on the fused HIP forward / backward "
+                         "(h12env.policy.TrainableFusedMLP; agent.algorithm.fused_learner=true works too)")
     AppLauncher.add_app_launcher_args(ap)
     return ap
 
@@ -85,6 +88,8 @@ def apply_cli(agent_cfg, env_cfg, args):
             s["mirror_loss_coeff"] = args.mirror_loss_coeff
         else:
             s.mirror_loss_coeff = args.mirror_loss_coeff
+    if getattr(args, "fused_learner", False):
+        agent_cfg.algorithm.fused_learner = True
     if getattr(args, "privileged_critic", False):
         from h12env.cfg import enable_privileged_critic
 

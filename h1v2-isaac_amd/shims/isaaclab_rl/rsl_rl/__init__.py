@@ -48,6 +48,8 @@ class RslRlPpoAlgorithmCfg:
     normalize_advantage_per_mini_batch: bool = False
     symmetry_cfg: RslRlSymmetryCfg | dict | None = None
     rnd_cfg: dict | None = None
+    # h12env.ppo extension: actor and critic of the update on the fused HIP forward / backward (None: H12_LEARNER_FUSED)
+    fused_learner: bool | None = None
 
 
 @dataclass

@@ -1,4 +1,5 @@
-/* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip).
+/* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
+ * csrc/h12_policy_train.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
@@ -115,6 +116,49 @@ int h12learn_mlp_pack(const h12learn_mlp_desc* desc, float* packed, void* stream
  * than 64 KiB of LDS: the first such call of a process raises the kernel's limit (make it outside a capture). */
 int h12learn_mlp_forward(const h12learn_mlp_desc* desc, const float* packed, const float* x, long long n,
                          float* const* y, void* stream);
+
+/* ---- training side of the fused policy MLP (csrc/h12_policy_train.hip): forward that keeps the hidden activations,
+ * and the backward through every layer, one launch each, on the same exact-fp32 MFMA design.  ONE network per call
+ * (desc.n_nets == 1) and H12LEARN_MLP_NORM_NONE only; every width, the input included, at most
+ * h12learn_mlp_train_max_width().  The weight gradients dW_l = dZ_l^T H_{l-1} are left to the caller's GEMM library.
+ * Blocks own h12learn_mlp_train_rows() rows; more than 64 KiB of LDS are needed for wide networks, and the first such
+ * call of either kernel raises its limit: that call fails with H12LEARN_E_HIP when its stream is capturing. */
+
+/* Rows of a block of the training kernels (the row tile R); a query so tests can place n at R-1, R, R+1, 2R+1. */
+int h12learn_mlp_train_rows(void);
+
+/* The largest supported width of any layer of the training kernels, the input included (>= 512). */
+int h12learn_mlp_train_max_width(void);
+
+/* Bytes of the transposed packed weights of desc (shapes only); 0 with h12learn_last_error set when invalid. */
+size_t h12learn_mlp_packed_t_bytes(const h12learn_mlp_desc* desc);
+
+/* One launch: every W of desc into the tiled, zero-padded layout of h12learn_mlp_pack taken over W^T (per layer
+ * [16-column tile of the layer's INPUT][k-group of its OUTPUT][lane][4], no bias): the B operand of the dgrad
+ * dH = dZ W.  packed_t: 16-byte aligned, h12learn_mlp_packed_t_bytes.  Run after every change of the weights; it may
+ * be captured.  The b pointers of desc are not read. */
+int h12learn_mlp_pack_t(const h12learn_mlp_desc* desc, float* packed_t, void* stream);
+
+/* One launch: y ([n][d_out]) = the network of desc on x ([n][d_in] contiguous fp32) from packed (h12learn_mlp_pack of
+ * the same desc), bit-identical to h12learn_mlp_forward, and h[l] ([n][dims[l+1]], l < n_layers - 1) = the ELU output
+ * of hidden layer l.  h may be null for a single layer. */
+int h12learn_mlp_forward_train(const h12learn_mlp_desc* desc, const float* packed, const float* x, long long n,
+                               float* y, float* const* h, void* stream);
+
+/* Bytes of workspace h12learn_mlp_backward needs for n rows (the per-block bias-gradient partials); it needs no
+ * initialisation.  0 with h12learn_last_error set when desc or n is invalid. */
+size_t h12learn_mlp_backward_workspace_bytes(const h12learn_mlp_desc* desc, long long n);
+
+/* Two launches.  dy is [n][d_out], h[l] the activations h12learn_mlp_forward_train saved, packed_t the transposed pack.
+ * With dZ_{L-1} = dy, for l = L-2 .. 0:  dH_l = dZ_{l+1} W_{l+1},  dZ_l = dH_l * f'(h_l),  f'(h) = h > 0 ? 1 : h + 1
+ * (ELU's derivative from its output).  Writes dz[l] ([n][dims[l+1]], l < L - 1), dx ([n][d_in]) = dZ_0 W_0 when dx is
+ * not null, and every bias gradient db[l][j] = sum_r dZ_l[r][j] (l < L; db[L-1] sums dy).  A dZ / dx element is one
+ * fmaf chain from zero whose order depends on the summed layer's width alone; db sums each block's rows in row order
+ * and the blocks in block-index order (second launch), without atomics: everything is bitwise reproducible.  The W / b
+ * pointers of desc are not read. */
+int h12learn_mlp_backward(const h12learn_mlp_desc* desc, const float* packed_t, const float* dy,
+                          const float* const* h, long long n, float* const* dz, float* const* db, float* dx,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 const char* h12learn_last_error(void);
 

@@ -25,11 +25,21 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm is required to build libh12env.so)")
 
 
+# the translation units of libh12env.so, in link order
+UNITS = [CSRC / n for n in ("h12env.hip", "h12_learn.hip", "h12_policy.hip", "h12_policy_train.hip", "h12_priv.hip",
+                            "h12_render.hip")]
+# -fno-slp-vectorize: packed-fp32 SLP code needs register pairs and costs ~30 % extra v_mov here.
+# -ffinite-math-only -fno-signed-zeros: the state is finite by construction, so products with
+# the model's zero constants fold away and fminf/fmaxf need no NaN canonicalisation (-21 % VALU
+# in the inner physics step); results of finite operations are unchanged.  Device code only: the
+# host-side config validation keeps its NaN checks.
+FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Xarch_device", "-ffinite-math-only",
+         "-Xarch_device", "-fno-signed-zeros", "-fPIC", "-Wall", "-Wno-unused-function"]
+
+
 def sources():
-    return [CSRC / "h12env.hip", CSRC / "h12_learn.hip", CSRC / "h12_policy.hip", CSRC / "h12_policy_train.hip",
-            CSRC / "h12_math.h", CSRC / "h12_model_gen.h",
-            REPO / "include" / "h12env.h", REPO / "include" / "h12learn.h", REPO / "include" / "h12render.h",
-            REPO / "include" / "h12priv.h", CSRC / "h12_priv.hip", CSRC / "h12_render.hip"]
+    return [CSRC / "h12_math.h", CSRC / "h12_model_gen.h", CSRC / "h12_mlp_core.h", REPO / "include" / "h12env.h",
+            REPO / "include" / "h12learn.h", REPO / "include" / "h12render.h", REPO / "include" / "h12priv.h"] + UNITS
 
 
 def source_sha256() -> str:
@@ -59,16 +69,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags: list[str] | No
                    stdout=subprocess.DEVNULL)
     if not force and not needs_build():
         return OUT
-    # -fno-slp-vectorize: packed-fp32 SLP code needs register pairs and costs ~30 % extra v_mov here.
-    # -ffinite-math-only -fno-signed-zeros: the state is finite by construction, so products with
-    # the model's zero constants fold away and fminf/fmaxf need no NaN canonicalisation (-21 % VALU
-    # in the inner physics step); results of finite operations are unchanged.  Device code only: the
-    # host-side config validation keeps its NaN checks.
-    cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Xarch_device",
-           "-ffinite-math-only", "-Xarch_device", "-fno-signed-zeros", "-fPIC", "-shared", "-Wall",
-           "-Wno-unused-function", "-o", str(OUT), str(CSRC / "h12env.hip"), str(CSRC / "h12_learn.hip"),
-           str(CSRC / "h12_policy.hip"), str(CSRC / "h12_policy_train.hip"), str(CSRC / "h12_priv.hip"),
-           str(CSRC / "h12_render.hip")]
+    cmd = [hipcc(), *FLAGS, "-shared", "-o", str(OUT), *map(str, UNITS)]
     if extra_flags:
         cmd += extra_flags
     if verbose:

@@ -12,6 +12,10 @@ The packed copy of the weights is what the kernel reads: ``refresh()`` (one laun
 live parameters, so call it, or pass ``repack=True``, after the parameters changed.  No autograd.  On CPU tensors the
 torch modules are evaluated, so the surface is testable without a GPU; on CUDA a missing kernel is an error.
 
+Inside a captured graph: networks wider than 512 need more than 64 KiB of LDS, and the first such call of a process
+raises the kernel's limit, which cannot be done while the stream is capturing: that call raises "must be made outside
+a stream capture (warm up first)".  Call once eagerly before capturing, as any graph warm-up does.
+
 ``TrainableFusedMLP`` (further down) is the learner's counterpart: one network with autograd, forward and backward on
 the training kernels of csrc/h12_policy_train.hip; ``FusedMLP`` itself stays forward only."""
 from __future__ import annotations

@@ -113,7 +113,8 @@ int h12learn_mlp_pack(const h12learn_mlp_desc* desc, float* packed, void* stream
  * from the weights in packed (the W / b pointers of desc are not read).  An output element is
  * bias + sum_k h[k] W[j][k] accumulated as one fmaf chain whose k order depends on the layer's input width alone, so
  * a row's result does not depend on n, on its position or on the other rows.  Networks wider than 512 need more
- * than 64 KiB of LDS: the first such call of a process raises the kernel's limit (make it outside a capture). */
+ * than 64 KiB of LDS: the first such call of a process raises the kernel's limit, and fails with H12LEARN_E_HIP
+ * ("must be made outside a stream capture (warm up first)") when its stream is capturing. */
 int h12learn_mlp_forward(const h12learn_mlp_desc* desc, const float* packed, const float* x, long long n,
                          float* const* y, void* stream);
 

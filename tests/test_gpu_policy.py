@@ -10,7 +10,9 @@ Gate 2  accuracy against an fp64 evaluation of the same fp32 parameters and inpu
             e_h = e_z + 4u |h|                               (ELU is 1-Lipschitz; expm1f within a few ulp)
         measured on the MI355X (worst fraction of the bound over every shape below): fused 0.226, torch fp32 0.220
         (the single layer with 3 inputs; 4e-6 on 451-512-256-128-12, where the compounded bound is loose).
-Gate 3  bitwise properties: run to run, row-subset invariance, two networks == two calls, NaN containment, re-pack.
+Gate 3  bitwise properties: run to run, row-subset invariance, two networks == two calls, NaN containment, re-pack;
+        the first call over 64 KiB of LDS is refused inside a stream capture (inference and training kernels, in a
+        fresh process: tests/helpers/lds_limit_child.py).
 Gate 4  integration at 64 envs: both trainers' collection with H12_POLICY_FUSED=1 (graphed == eager bit for bit, inside
         gate 2 of the default path), play.py --fused and sim2sim.py --fused in a subprocess each,
         get_inference_policy(fused=True).
@@ -288,6 +290,16 @@ def test_forward_and_pack_inside_a_captured_graph(bitwise_setup):
     g.replay()  # the replay re-packs the changed weights and reads the new input
     new = FusedMLP(nets, normalizer=norm)(x.flip(0).contiguous())
     assert all(torch.equal(a, b) for a, b in zip(out, new))
+
+
+def test_first_call_over_64_kib_of_lds_is_refused_inside_a_capture(gpu):
+    # the raised-limit flags are one per kernel and process: only a fresh process makes a first call
+    child = ROOT / "tests" / "helpers" / "lds_limit_child.py"
+    p = subprocess.run(["timeout", "-k", "10", "120", sys.executable, str(child)], capture_output=True, text=True)
+    print(p.stdout)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    for kernel in ("mlp_forward", "mlp_forward_train", "mlp_backward"):
+        assert f"ok {kernel}\n" in p.stdout, kernel
 
 
 # ---------------------------------------------------------------------------------------------- gate 4

@@ -2,9 +2,10 @@
 """Static ISA report of libh12env's kernels (gfx950): register allocation from the code-object metadata and
 instruction counts from the compiler's own assembly.
 
-    python tools/kernel_isa.py [kernel-name-substring ...] [--json profiles/latest_isa.json]
+    python tools/kernel_isa.py [kernel-name-substring ...] [--source h12_policy.hip] [--json profiles/latest_isa.json]
 
-Builds csrc/h12env.hip with -save-temps into a temp dir (same flags as h12env.build), then for each kernel
+Builds one translation unit of csrc/ (--source, default h12env.hip) with -save-temps into a temp dir (same flags as
+h12env.build), then for each kernel (of another source than h12env.hip: every kernel unless substrings are given)
 prints .vgpr_count / .agpr_count / .sgpr_count / scratch, the instruction mix (VALU, v_accvgpr moves, SALU,
 vector / scalar memory, s_waitcnt) and every loop body (backward branch) with its VALU count.
 
@@ -26,12 +27,14 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "h1v2-isaac_amd"))
 
 
-def build_asm(tmp: Path) -> Path:
-    from h12env.build import ARCH, CSRC, hipcc
+DEFAULT_SOURCE = "h12env.hip"
 
-    cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Xarch_device",
-           "-ffinite-math-only", "-Xarch_device", "-fno-signed-zeros", "-fPIC", "-shared", "-save-temps",
-           "-Wno-unused-function", "-o", str(tmp / "lib.so"), str(CSRC / "h12env.hip")]
+
+def build_asm(tmp: Path, source: str = DEFAULT_SOURCE) -> Path:
+    from h12env.build import ARCH, CSRC, FLAGS, hipcc
+
+    # -c: the other translation units' symbols stay unresolved
+    cmd = [hipcc(), *FLAGS, "-c", "-save-temps", "-o", str(tmp / "tu.o"), str(CSRC / source)]
     subprocess.run(cmd, check=True, cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     s = sorted(tmp.glob(f"*{ARCH}*.s"))
     if not s:
@@ -129,9 +132,16 @@ def main():
         i = args.index("--json")
         js = Path(args[i + 1])
         del args[i:i + 2]
-    subs = args or ["step_kernelILi0E", "obs_assemble_kernelILi10E"]
+    source = DEFAULT_SOURCE
+    if "--source" in args:
+        i = args.index("--source")
+        source = args[i + 1]
+        del args[i:i + 2]
+    if js is not None and source != DEFAULT_SOURCE:
+        sys.exit(f"--json describes {DEFAULT_SOURCE}'s step kernel: not with --source {source}")
+    subs = args or (["step_kernelILi0E", "obs_assemble_kernelILi10E"] if source == DEFAULT_SOURCE else [""])
     with tempfile.TemporaryDirectory() as td:
-        text = build_asm(Path(td)).read_text()
+        text = build_asm(Path(td), source).read_text()
     meta = metadata(text)
     print("isa_sha256", isa_sha256(text))
     if js is not None:

@@ -1,0 +1,364 @@
+// h12_ppo_head.hip: the fused PPO loss head of libh12env.so (include/h12learn.h, h12learn_ppo_head): gather, Gaussian
+// log-probability, KL, clipped surrogate, clipped value loss, their weighted sum and its gradients with respect to the
+// actor's mean, the critic's value and the std parameter, in two launches.
+//
+//   1. ppo_head_rows_kernel<G>   a block owns HEAD_ROWS rows.  A row is a group of G lanes (G = 16 for A <= 16, else
+//      32), lane a of the group its action a, and a wave's groups are consecutive rows: the wave's loads of mean (and of
+//      directly read actions) cover 64 / G consecutive rows, contiguous in memory, and the gathered rows of actions,
+//      old_mu and old_sigma are A contiguous floats each.  A wave takes its HEAD_UNROLL passes' loads in two batches
+//      (indices; then everything addressed by them; nothing is used before the last load is issued).  The sums over a
+//      row's actions are xor-butterflies inside the group (a fixed order, every lane of the group gets the same bits).
+//      Lane 0 of a group holds the row's scalars (old log-probability, advantage, return, target value, value),
+//      computes ratio, both surrogates, the value loss and d_value, and broadcasts d loss / d log_prob to its group.
+//      The rows' surrogate / value / KL terms and their d_param terms go to LDS; after one barrier 3 + A threads add
+//      them in row order and write the block's partial sums.
+//   2. ppo_head_fold_kernel      one block.  The partials are staged through LDS in chunks (coalesced, all loads in
+//      flight) and thread j adds quantity j in block-index order.  Thread 0 then forms the means, the entropy, the
+//      total, the learning-rate rule and the statistics; threads 3 .. 3 + A finish d_param.
+//
+// No atomics, no counters, nothing to initialise: every output is a fixed-order sum.  The summed terms are fp32, the
+// accumulators and the partials fp64, so a sum carries the rounding of its terms only.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/h12learn.h"
+
+// the error record of h12_learn.hip (not part of the ABI)
+int h12_learn_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3), visibility("hidden")));
+
+namespace {
+
+constexpr int HEAD_WAVES = 4;
+constexpr int HEAD_ROWS = 64;        // rows per block R
+constexpr int HEAD_UNROLL = 4;       // passes whose loads are in flight together
+constexpr int HEAD_MAX_A = 32;
+constexpr int HEAD_SC = 3;           // per-row scalars that are summed: surrogate, value, KL
+constexpr int FOLD_THREADS = 256;
+constexpr int FOLD_CHUNK = 128;      // blocks staged in LDS at a time
+constexpr int FOLD_PER_THREAD = (FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A) + FOLD_THREADS - 1) / FOLD_THREADS;
+constexpr int SUM_BATCH = 8;        // LDS reads in flight ahead of a serial sum
+constexpr double LOG_SQRT_2PI_D = 0.918938533204672741780329736406;  // log(sqrt(2 pi)), also 0.5 log(2 pi)
+constexpr float LOG_SQRT_2PI = (float)LOG_SQRT_2PI_D;
+
+struct HeadScalars {
+  float lo, hi;      // 1 -+ clip_param
+  float clip;        // the value clip
+  float vcoef, ecoef;
+  float kl_up, kl_down;  // 2 desired_kl, desired_kl / 2
+};
+
+#define HEAD_HIP_TRY(expr)                                                                  \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess) {                                                                 \
+      (void)hipGetLastError();                                                              \
+      return h12_learn_fail(H12LEARN_E_HIP, "%s: %s", #expr, hipGetErrorString(_e));        \
+    }                                                                                       \
+  } while (0)
+
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
+  return v;
+}
+
+// torch.max's backward weights of x against y: (weight of x, weight of y)
+__device__ __forceinline__ void max_weights(float x, float y, float& wx, float& wy) {
+  wx = x > y ? 1.0f : (x == y ? 0.5f : 0.0f);
+  wy = x < y ? 1.0f : (x == y ? 0.5f : 0.0f);
+}
+
+template <int G>
+__global__ __launch_bounds__(HEAD_WAVES * 64) void ppo_head_rows_kernel(h12learn_ppo_head_args p, HeadScalars sc,
+                                                                        double* partial) {
+#pragma clang fp contract(off)
+  constexpr int GROUPS = 64 / G;                    // rows of a wave per pass
+  constexpr int PASS_ROWS = HEAD_WAVES * GROUPS;    // rows of the block per pass
+  constexpr int PASSES = HEAD_ROWS / PASS_ROWS;
+  static_assert(PASSES % HEAD_UNROLL == 0, "the passes are taken HEAD_UNROLL at a time");
+  static_assert(HEAD_ROWS % SUM_BATCH == 0, "the row sums read SUM_BATCH rows at a time");
+  __shared__ float s_dp[HEAD_ROWS][G];
+  __shared__ float s_sc[HEAD_ROWS][HEAD_SC + 1];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int a = lane & (G - 1), grp = lane / G;
+  const int A = p.A;
+  const bool col = a < A;
+  const int ac = col ? a : A - 1;  // lanes past A re-read the last column and contribute nothing
+  const long long m = p.m, B = p.B;
+  const float inv_m = 1.0f / (float)m;
+
+  // the lane's column of the std parameter
+  const float prm = p.std_param[ac];
+  const float sigma = p.std_kind == H12LEARN_PPO_STD_LOG ? expf(prm) : prm;
+  const float log_sigma = logf(sigma);
+  const float two_var = 2.0f * (sigma * sigma);
+  const float inv_sigma = 1.0f / sigma;
+  const float inv_var = inv_sigma * inv_sigma;
+
+  const long long block_row = (long long)blockIdx.x * HEAD_ROWS;
+  for (int p0 = 0; p0 < PASSES; p0 += HEAD_UNROLL) {
+    long long rr[HEAD_UNROLL], k[HEAD_UNROLL];
+    int rl[HEAD_UNROLL];
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 1: the indices
+      rl[i] = (p0 + i) * PASS_ROWS + w * GROUPS + grp;
+      const long long r = block_row + rl[i];
+      rr[i] = r < m ? r : m - 1;  // rows past m re-read row m - 1 and store nothing
+      const long long rb = rr[i] >= B ? rr[i] - B : rr[i];
+      k[i] = p.idx ? p.idx[rb] : rb;
+    }
+    float mu[HEAD_UNROLL], act[HEAD_UNROLL], omu[HEAD_UNROLL], osg[HEAD_UNROLL];
+    float olp[HEAD_UNROLL], adv[HEAD_UNROLL], ret[HEAD_UNROLL], tv[HEAD_UNROLL], val[HEAD_UNROLL];
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 2: everything else
+      k[i] = k[i] < 0 ? 0 : (k[i] < p.n_src ? k[i] : p.n_src - 1);
+      const size_t er = (size_t)rr[i] * (size_t)A + ac, ek = (size_t)k[i] * (size_t)A + ac;
+      mu[i] = p.mean[er];
+      act[i] = p.actions[p.actions_direct ? er : ek];
+      omu[i] = 0.0f, osg[i] = 1.0f;
+      if (rr[i] < B) {  // the KL runs over the original samples only
+        omu[i] = p.old_mu[ek];
+        osg[i] = p.old_sigma[ek];
+      }
+      olp[i] = adv[i] = ret[i] = tv[i] = val[i] = 0.0f;
+      if (a == 0) {
+        olp[i] = p.old_log_prob[k[i]];
+        adv[i] = p.advantages[k[i]];
+        ret[i] = p.returns[k[i]];
+        tv[i] = p.target_values[k[i]];
+        val[i] = p.value[rr[i]];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {
+      const bool live = block_row + rl[i] < m;
+      const float d = act[i] - mu[i];
+      const float dd = d * d;
+      const float lp_a = -dd / two_var - log_sigma - LOG_SQRT_2PI;
+      const float dm = omu[i] - mu[i];
+      const float kl_a = logf(sigma / osg[i] + 1.0e-5f) + (osg[i] * osg[i] + dm * dm) / two_var - 0.5f;
+      const float log_prob = group_sum<G>(col ? lp_a : 0.0f);
+      const float kl = group_sum<G>(col ? kl_a : 0.0f);
+      float g_lp = 0.0f;
+      if (a == 0) {
+        const float ratio = expf(log_prob - olp[i]);
+        const float s1 = -adv[i] * ratio;
+        const float s2 = -adv[i] * fminf(fmaxf(ratio, sc.lo), sc.hi);
+        const bool inside = ratio >= sc.lo && ratio <= sc.hi;
+        float w1, w2;
+        max_weights(s1, s2, w1, w2);
+        g_lp = inv_m * (-adv[i] * (w1 + (inside ? w2 : 0.0f))) * ratio;
+        float vl, dv;
+        if (p.use_clipped_value_loss) {
+          const float dvt = val[i] - tv[i];
+          const float vc = tv[i] + fminf(fmaxf(dvt, -sc.clip), sc.clip);
+          const bool inside_v = dvt >= -sc.clip && dvt <= sc.clip;
+          const float e1 = val[i] - ret[i], e2 = vc - ret[i];
+          const float q1 = e1 * e1, q2 = e2 * e2;
+          float v1, v2;
+          max_weights(q1, q2, v1, v2);
+          vl = fmaxf(q1, q2);
+          dv = v1 * (2.0f * e1) + (inside_v ? v2 * (2.0f * e2) : 0.0f);
+        } else {
+          const float e = ret[i] - val[i];
+          vl = e * e;
+          dv = -2.0f * e;
+        }
+        if (live) p.d_value[rr[i]] = (sc.vcoef * inv_m) * dv;
+        s_sc[rl[i]][0] = live ? fmaxf(s1, s2) : 0.0f;
+        s_sc[rl[i]][1] = live ? vl : 0.0f;
+        s_sc[rl[i]][2] = live && rr[i] < B ? kl : 0.0f;
+      }
+      g_lp = __shfl(g_lp, 0, G);
+      if (live && col) p.d_mean[(size_t)rr[i] * (size_t)A + a] = g_lp * (d * inv_var);
+      // d log_prob / d sigma = (actions - mean)^2 / sigma^3 - 1 / sigma
+      s_dp[rl[i]][a] = live && col ? g_lp * (dd * inv_var * inv_sigma - inv_sigma) : 0.0f;
+    }
+  }
+  __syncthreads();
+  // row-order sums: threads [0, A) of wave 0 take d_param's columns, threads [64, 64 + HEAD_SC) the scalars
+  // (fp64 accumulators: the sums then carry the rounding of their fp32 terms only)
+  double* out = partial + (size_t)blockIdx.x * (size_t)(HEAD_SC + A);
+  if (tid < A) {
+    double acc = 0.0;
+    for (int r = 0; r < HEAD_ROWS; r += SUM_BATCH) {  // SUM_BATCH reads in flight ahead of the dependent adds
+      float v[SUM_BATCH];
+#pragma unroll
+      for (int j = 0; j < SUM_BATCH; ++j) v[j] = s_dp[r + j][tid];
+#pragma unroll
+      for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
+    }
+    out[HEAD_SC + tid] = acc;
+  } else if (tid >= 64 && tid < 64 + HEAD_SC) {
+    const int q = tid - 64;
+    double acc = 0.0;
+    for (int r = 0; r < HEAD_ROWS; r += SUM_BATCH) {
+      float v[SUM_BATCH];
+#pragma unroll
+      for (int j = 0; j < SUM_BATCH; ++j) v[j] = s_sc[r + j][q];
+#pragma unroll
+      for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
+    }
+    out[q] = acc;
+  }
+}
+
+__global__ __launch_bounds__(FOLD_THREADS) void ppo_head_fold_kernel(h12learn_ppo_head_args p, HeadScalars sc,
+                                                                      const double* partial, int blocks) {
+#pragma clang fp contract(off)
+  __shared__ double s_buf[FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)];
+  __shared__ double s_fin[HEAD_SC + HEAD_MAX_A];
+  __shared__ double s_ent[HEAD_MAX_A];
+  const int tid = threadIdx.x;
+  const int P = HEAD_SC + p.A;
+  const bool is_log = p.std_kind == H12LEARN_PPO_STD_LOG;
+  // issued before the partials are touched, so these latencies overlap the sums
+  const float prm = tid >= HEAD_SC && tid < P ? p.std_param[tid - HEAD_SC] : 0.0f;
+  const float lr = tid == 0 && p.lr ? *p.lr : 0.0f;
+  float st[3] = {0.0f, 0.0f, 0.0f};
+  if (tid == 0 && p.stats_accum) st[0] = p.stats_accum[0], st[1] = p.stats_accum[1], st[2] = p.stats_accum[2];
+  double acc = 0.0;
+  for (int c0 = 0; c0 < blocks; c0 += FOLD_CHUNK) {
+    const int cnt = blocks - c0 < FOLD_CHUNK ? blocks - c0 : FOLD_CHUNK;
+    const int total = cnt * P;
+    const double* src = partial + (size_t)c0 * (size_t)P;
+    double stage[FOLD_PER_THREAD];  // every load of the chunk issued before the first LDS store
+#pragma unroll
+    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
+      const int i = tid + j * FOLD_THREADS;
+      stage[j] = i < total ? src[i] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
+      const int i = tid + j * FOLD_THREADS;
+      if (i < total) s_buf[i] = stage[j];
+    }
+    __syncthreads();
+    if (tid < P) {
+      // block-index order; SUM_BATCH reads in flight ahead of the dependent adds (a tail adds +0.0: no change)
+      for (int b = 0; b < cnt; b += SUM_BATCH) {
+        double v[SUM_BATCH];
+#pragma unroll
+        for (int j = 0; j < SUM_BATCH; ++j) v[j] = b + j < cnt ? s_buf[(b + j) * P + tid] : 0.0;
+#pragma unroll
+        for (int j = 0; j < SUM_BATCH; ++j) acc += v[j];
+      }
+    }
+    __syncthreads();  // the buffer is reused by the next chunk
+  }
+  if (tid < P) s_fin[tid] = acc;
+  if (tid >= HEAD_SC && tid < P) {
+    // d loss / d sigma = sum_r (...) - entropy_coef / sigma; the log parameter's gradient is that times sigma
+    const float sigma = is_log ? expf(prm) : prm;
+    const double g = acc - (double)sc.ecoef / (double)sigma;
+    p.d_param[tid - HEAD_SC] = (float)(is_log ? g * (double)sigma : g);
+    s_ent[tid - HEAD_SC] = (0.5 + LOG_SQRT_2PI_D) + (double)logf(sigma);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double ent_sum = 0.0;
+    for (int a = 0; a < p.A; ++a) ent_sum += s_ent[a];
+    const double surr_d = s_fin[0] / (double)p.m, vl_d = s_fin[1] / (double)p.m;
+    const float surr = (float)surr_d, vl = (float)vl_d, ent = (float)ent_sum;
+    const float kl = (float)(s_fin[2] / (double)p.B);
+    p.out[0] = surr;
+    p.out[1] = vl;
+    p.out[2] = ent;
+    p.out[3] = kl;
+    p.out[4] = (float)(surr_d + (double)sc.vcoef * vl_d - (double)sc.ecoef * ent_sum);
+    if (p.lr) {
+      float next = lr;
+      if (kl > sc.kl_up)
+        next = fmaxf(lr * (1.0f / 1.5f), 1.0e-5f);  // torch divides by a host scalar as a product with its reciprocal
+      else if (kl > 0.0f && kl < sc.kl_down)
+        next = fminf(lr * 1.5f, 1.0e-2f);
+      *p.lr = next;
+    }
+    if (p.stats_accum) {
+      p.stats_accum[0] = st[0] + vl;
+      p.stats_accum[1] = st[1] + surr;
+      p.stats_accum[2] = st[2] + ent;
+    }
+  }
+}
+
+long long head_blocks(long long m) { return (m + HEAD_ROWS - 1) / HEAD_ROWS; }
+
+}  // namespace
+
+extern "C" {
+
+int h12learn_ppo_head_rows(void) { return HEAD_ROWS; }
+
+int h12learn_ppo_head_max_actions(void) { return HEAD_MAX_A; }
+
+size_t h12learn_ppo_head_workspace_bytes(long long m, int A) {
+  if (m < 1) {
+    h12_learn_fail(H12LEARN_E_ARG, "ppo_head_workspace_bytes: m = %lld (must be >= 1)", m);
+    return 0;
+  }
+  if (A < 1 || A > HEAD_MAX_A) {
+    h12_learn_fail(H12LEARN_E_ARG, "ppo_head_workspace_bytes: A = %d (1 .. %d)", A, HEAD_MAX_A);
+    return 0;
+  }
+  return (size_t)head_blocks(m) * (size_t)(HEAD_SC + A) * sizeof(double);
+}
+
+int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream) {
+  if (!args) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: args is null");
+  const h12learn_ppo_head_args& p = *args;
+  if (p.m < 1) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld (must be >= 1)", p.m);
+  if (p.B < 1 || (p.m != p.B && p.m != 2 * p.B))
+    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld is neither B nor 2 B (B = %lld)", p.m, p.B);
+  if (p.A < 1 || p.A > HEAD_MAX_A) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: A = %d (1 .. %d)", p.A, HEAD_MAX_A);
+  if (p.n_src < 1) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: n_src = %lld (must be >= 1)", p.n_src);
+  if (!p.idx && p.B > p.n_src)
+    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: B = %lld rows of sources of n_src = %lld without idx", p.B,
+                          p.n_src);
+  if (p.std_kind != H12LEARN_PPO_STD_SCALAR && p.std_kind != H12LEARN_PPO_STD_LOG)
+    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: std_kind = %d (H12LEARN_PPO_STD_SCALAR or _LOG)", p.std_kind);
+  const struct {
+    const void* ptr;
+    const char* name;
+  } required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.std_param, "std_param"}, {p.old_log_prob, "old_log_prob"},
+                  {p.advantages, "advantages"}, {p.returns, "returns"}, {p.target_values, "target_values"},
+                  {p.old_mu, "old_mu"}, {p.old_sigma, "old_sigma"}, {p.actions, "actions"}, {p.d_mean, "d_mean"},
+                  {p.d_value, "d_value"}, {p.d_param, "d_param"}, {p.out, "out"}, {p.workspace, "workspace"}};
+  for (const auto& q : required)
+    if (!q.ptr) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: %s is null", q.name);
+  if (!(p.clip_param >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: clip_param = %g (must be >= 0)", p.clip_param);
+  if (p.lr && !(p.desired_kl > 0.0))
+    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: desired_kl = %g with lr set (must be > 0)", p.desired_kl);
+  const size_t need = h12learn_ppo_head_workspace_bytes(p.m, p.A);
+  if (p.workspace_bytes < need)
+    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: workspace_bytes = %zu, %zu needed", p.workspace_bytes, need);
+  if (((uintptr_t)p.workspace & 7) != 0) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: workspace is not 8-byte aligned");
+  const long long blocks = head_blocks(p.m);
+  if (blocks > 0x7fffffffLL) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld exceeds the grid", p.m);
+
+  HeadScalars sc;
+  sc.lo = (float)(1.0 - p.clip_param);
+  sc.hi = (float)(1.0 + p.clip_param);
+  sc.clip = (float)p.clip_param;
+  sc.vcoef = (float)p.value_loss_coef;
+  sc.ecoef = (float)p.entropy_coef;
+  sc.kl_up = (float)(p.desired_kl * 2.0);
+  sc.kl_down = (float)(p.desired_kl / 2.0);
+  hipStream_t s = (hipStream_t)stream;
+  double* partial = (double*)p.workspace;
+  if (p.A <= 16)
+    hipLaunchKernelGGL(ppo_head_rows_kernel<16>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc, partial);
+  else
+    hipLaunchKernelGGL(ppo_head_rows_kernel<32>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc, partial);
+  HEAD_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ppo_head_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, s, p, sc, (const double*)partial,
+                     (int)blocks);
+  HEAD_HIP_TRY(hipGetLastError());
+  return H12LEARN_OK;
+}
+
+}  // extern "C"

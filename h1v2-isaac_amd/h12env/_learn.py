@@ -15,7 +15,8 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_mlp_forward", "h12learn_mirror_rows", "h12learn_mlp_train_rows",
                  "h12learn_mlp_train_max_width", "h12learn_mlp_packed_t_bytes", "h12learn_mlp_pack_t",
                  "h12learn_mlp_forward_train", "h12learn_mlp_backward_workspace_bytes", "h12learn_mlp_backward",
-                 "h12learn_last_error"]
+                 "h12learn_ppo_head_rows", "h12learn_ppo_head_max_actions", "h12learn_ppo_head_workspace_bytes",
+                 "h12learn_ppo_head", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -32,6 +33,23 @@ class MlpDesc(C.Structure):
     """h12learn_mlp_desc"""
     _fields_ = [("n_nets", C.c_int), ("d_in", C.c_int), ("norm_kind", C.c_int), ("norm_eps", C.c_float),
                 ("norm_mean", C.c_void_p), ("norm_scale", C.c_void_p), ("nets", MlpNet * MLP_MAX_NETS)]
+
+
+PPO_STD_SCALAR, PPO_STD_LOG = 0, 1
+
+
+class PpoHeadArgs(C.Structure):
+    """h12learn_ppo_head_args"""
+    _fields_ = [("m", C.c_longlong), ("B", C.c_longlong), ("n_src", C.c_longlong), ("A", C.c_int), ("std_kind", C.c_int),
+                ("actions_direct", C.c_int), ("use_clipped_value_loss", C.c_int), ("mean", C.c_void_p),
+                ("value", C.c_void_p), ("std_param", C.c_void_p), ("idx", C.c_void_p), ("old_log_prob", C.c_void_p),
+                ("advantages", C.c_void_p), ("returns", C.c_void_p), ("target_values", C.c_void_p),
+                ("old_mu", C.c_void_p), ("old_sigma", C.c_void_p), ("actions", C.c_void_p), ("clip_param", C.c_double),
+                ("value_loss_coef", C.c_double), ("entropy_coef", C.c_double), ("desired_kl", C.c_double),
+                ("d_mean", C.c_void_p), ("d_value", C.c_void_p), ("d_param", C.c_void_p), ("out", C.c_void_p),
+                ("lr", C.c_void_p), ("stats_accum", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
 
 _bound = None
 
@@ -80,6 +98,14 @@ def learn_library():
     lib.h12learn_mlp_backward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.POINTER(C.c_void_p), C.c_longlong,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, C.c_size_t, vp]
     lib.h12learn_mlp_backward.restype = C.c_int
+    lib.h12learn_ppo_head_rows.argtypes = []
+    lib.h12learn_ppo_head_rows.restype = C.c_int
+    lib.h12learn_ppo_head_max_actions.argtypes = []
+    lib.h12learn_ppo_head_max_actions.restype = C.c_int
+    lib.h12learn_ppo_head_workspace_bytes.argtypes = [C.c_longlong, C.c_int]
+    lib.h12learn_ppo_head_workspace_bytes.restype = C.c_size_t
+    lib.h12learn_ppo_head.argtypes = [C.POINTER(PpoHeadArgs), vp]
+    lib.h12learn_ppo_head.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -324,3 +350,76 @@ def mlp_backward(desc: MlpDesc, packed_t: torch.Tensor, dy: torch.Tensor, hs, ne
                                           arr(dbs), None if dx is None else dx.data_ptr(), ws.data_ptr(), nbytes,
                                           _stream(dev)), "h12learn_mlp_backward")
     return dzs, dbs, dx
+
+
+# ---- fused PPO loss head (csrc/h12_ppo_head.hip)
+def ppo_head_rows() -> int:
+    return learn_library().h12learn_ppo_head_rows()
+
+
+def ppo_head_max_actions() -> int:
+    return learn_library().h12learn_ppo_head_max_actions()
+
+
+def ppo_head(mean: torch.Tensor, value: torch.Tensor, std_param: torch.Tensor, std_kind: int, idx, n_rows: int,
+             old_log_prob, advantages, returns, target_values, old_mu, old_sigma, actions, actions_direct: bool,
+             clip_param: float, value_loss_coef: float, entropy_coef: float, use_clipped_value_loss: bool,
+             lr: torch.Tensor | None = None, desired_kl: float | None = None, stats_accum: torch.Tensor | None = None):
+    """Two launches: (d_mean [m][A], d_value [m], d_param [A], out [5]) of the PPO loss head on mean [m][A], value
+    (m elements) and the std parameter [A].  ``n_rows`` is B, the minibatch's rows (m, or m / 2 under augmentation);
+    idx (None, or B int64 entries) selects the rows of the rollout tensors (n_src rows each; actions [m][A] with
+    ``actions_direct``).  ``lr`` (a device scalar; needs desired_kl) and ``stats_accum`` (3 floats) are updated in place
+    when given.  include/h12learn.h has the formulae."""
+    lib = learn_library()
+    _f32(mean, "mean"), _f32(value, "value"), _f32(std_param, "std_param")
+    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 1:
+        raise ValueError(f"ppo_head: mean {tuple(mean.shape)} is not (m >= 1, A >= 1)")
+    m, A = mean.shape
+    dev = mean.device
+    if value.numel() != m or std_param.numel() != A:
+        raise ValueError(f"ppo_head: value has {value.numel()} and std_param {std_param.numel()} elements for mean "
+                         f"{tuple(mean.shape)}")
+    B = int(n_rows)
+    n_src = old_log_prob.numel()
+    for name, t in (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns", returns),
+                    ("target_values", target_values)):
+        if _f32(t, name).numel() != n_src:
+            raise ValueError(f"ppo_head: {name} must have {n_src} elements")
+    for name, t in (("old_mu", old_mu), ("old_sigma", old_sigma)):
+        if _f32(t, name).shape != (n_src, A):
+            raise ValueError(f"ppo_head: {name} must be ({n_src}, {A})")
+    if _f32(actions, "actions").shape != ((m, A) if actions_direct else (n_src, A)):
+        raise ValueError(f"ppo_head: actions {tuple(actions.shape)} for m = {m}, n_src = {n_src}, "
+                         f"actions_direct = {bool(actions_direct)}")
+    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
+                                and idx.shape == (B,)):
+        raise ValueError(f"ppo_head: idx must be a contiguous int64 CUDA tensor of {B} entries")
+    if lr is not None and (_f32(lr, "lr").numel() != 1 or desired_kl is None):
+        raise ValueError("ppo_head: lr must be one float32 element and needs desired_kl")
+    if stats_accum is not None and _f32(stats_accum, "stats_accum").numel() < 3:
+        raise ValueError("ppo_head: stats_accum must have at least 3 elements")
+    nbytes = lib.h12learn_ppo_head_workspace_bytes(m, A)
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_ppo_head_workspace_bytes")
+    d_mean = torch.empty((m, A), dtype=torch.float32, device=dev)
+    d_value = torch.empty(m, dtype=torch.float32, device=dev)
+    d_param = torch.empty(A, dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    a = PpoHeadArgs()
+    a.m, a.B, a.n_src, a.A = m, B, n_src, A
+    a.std_kind, a.actions_direct = int(std_kind), int(bool(actions_direct))
+    a.use_clipped_value_loss = int(bool(use_clipped_value_loss))
+    a.mean, a.value, a.std_param = mean.data_ptr(), value.data_ptr(), std_param.data_ptr()
+    a.idx = None if idx is None else idx.data_ptr()
+    a.old_log_prob, a.advantages, a.returns = old_log_prob.data_ptr(), advantages.data_ptr(), returns.data_ptr()
+    a.target_values, a.old_mu, a.old_sigma = target_values.data_ptr(), old_mu.data_ptr(), old_sigma.data_ptr()
+    a.actions = actions.data_ptr()
+    a.clip_param, a.value_loss_coef, a.entropy_coef = float(clip_param), float(value_loss_coef), float(entropy_coef)
+    a.desired_kl = 0.0 if desired_kl is None else float(desired_kl)
+    a.d_mean, a.d_value, a.d_param, a.out = d_mean.data_ptr(), d_value.data_ptr(), d_param.data_ptr(), out.data_ptr()
+    a.lr = None if lr is None else lr.data_ptr()
+    a.stats_accum = None if stats_accum is None else stats_accum.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    _check(lib, lib.h12learn_ppo_head(C.byref(a), _stream(dev)), "h12learn_ppo_head")
+    return d_mean, d_value, d_param, out

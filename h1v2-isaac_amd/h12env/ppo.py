@@ -342,7 +342,8 @@ class PPO:
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
-                 symmetry_cfg: dict | None = None, fused_learner: bool | None = None, **kwargs):
+                 symmetry_cfg: dict | None = None, fused_learner: bool | None = None, fused_loss: bool | None = None,
+                 **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
@@ -391,6 +392,28 @@ class PPO:
             except ValueError as e:
                 raise ValueError(f"fused_learner: the policy's networks cannot run on the fused kernels "
                                  f"(Linear/ELU only, every width at most the kernels' maximum): {e}") from e
+        # opt-in: everything between the networks' outputs and loss.backward() as one autograd node on one HIP call
+        # (h12env.ppo_head.PPOHead).  None reads H12_PPO_HEAD_FUSED=1.  On CPU the node evaluates the torch
+        # expressions.  The default stays the torch path.
+        if fused_loss is None:
+            from .ppo_head import fused_loss_enabled
+
+            fused_loss = fused_loss_enabled()
+        self.fused_loss = bool(fused_loss)
+        if self.fused_loss:
+            from . import _learn
+
+            if normalize_advantage_per_mini_batch:
+                raise ValueError("fused_loss: normalize_advantage_per_mini_batch=True needs a two-pass mean / std over "
+                                 "the minibatch's advantages, which the fused loss head does not compute")
+            std_param = getattr(self.policy, "std", None) if getattr(self.policy, "noise_std_type", None) == "scalar" \
+                else getattr(self.policy, "log_std", None)
+            if std_param is None:
+                raise ValueError(f"fused_loss: {type(self.policy).__name__} has no state-independent std / log_std "
+                                 "parameter")
+            if std_param.numel() > _learn.ppo_head_max_actions():
+                raise ValueError(f"fused_loss: {std_param.numel()} actions, the fused loss head supports at most "
+                                 f"{_learn.ppo_head_max_actions()}")
         # rsl_rl 2.3 symmetry: mirror-image data augmentation and / or mirror loss; with both switches off the
         # symmetry loss is computed for logging only.  None: the update is untouched.
         self.symmetry = None
@@ -547,6 +570,8 @@ class PPO:
         """One PPO minibatch update (rsl_rl ppo.py update loop body): gather, forward, KL-adaptive learning
         rate, clipped surrogate + clipped value loss, backward, (all-reduce), grad clip, Adam, statistics.
         Host-sync free on the fused path, so it is also the body of the captured HIP graph."""
+        if self.fused_loss:
+            return self._minibatch_fused_loss(b, idx, stats)
         world = self.shard.world
         sym = self.symmetry
         aug = sym is not None and sym["use_data_augmentation"]
@@ -628,6 +653,77 @@ class PPO:
                                   symmetry_loss.detach()])
         else:
             stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()])
+
+    def _minibatch_fused_loss(self, b: dict, idx: torch.Tensor, stats: torch.Tensor):
+        """_minibatch with fused_loss: only the observations are gathered (and the actions where they are mirrored);
+        everything from get_actions_log_prob to loss is one PPOHead node, which on a single CUDA rank also applies
+        the adaptive schedule to _lr_t and, without symmetry, adds the statistics."""
+        from .ppo_head import HeadInputs, PPOHead
+
+        world = self.shard.world
+        sym = self.symmetry
+        aug = sym is not None and sym["use_data_augmentation"]
+        n_orig = idx.shape[0]
+        if aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
+            obs, actions = self._augment(b["observations"], b["actions"], idx, "policy")
+            critic_obs = (self._augment(b["privileged_observations"], None, idx, "critic")[0]
+                          if "privileged_observations" in b else obs)
+        else:
+            obs = b["observations"][idx]
+            critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
+            actions = b["actions"]  # the head gathers its rows
+        with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
+                            enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
+            self.policy.update_distribution(obs)
+            value = self.policy.evaluate(critic_obs).float()
+        if self.precision == "bf16":  # distribution statistics in fp32
+            self.policy.distribution = Normal(self.policy.distribution.mean.float(),
+                                              self.policy.distribution.stddev.float())
+        mean = self.policy.action_mean
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        on_device = mean.is_cuda
+        kind = self.policy.noise_std_type
+        head = HeadInputs(idx=idx, old_log_prob=b["actions_log_prob"], advantages=b["advantages"],
+                          returns=b["returns"], target_values=b["values"], old_mu=b["mu"], old_sigma=b["sigma"],
+                          actions=actions, actions_direct=aug, std_kind=kind, clip_param=self.clip_param,
+                          value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
+                          use_clipped_value_loss=self.use_clipped_value_loss,
+                          lr=self._lr_t if on_device and adaptive and world == 1 else None,
+                          desired_kl=self.desired_kl, stats_accum=stats if on_device and sym is None else None)
+        loss, out = PPOHead.apply(mean, value, self.policy.std if kind == "scalar" else self.policy.log_std, head)
+        if adaptive and head.lr is None:  # CPU, or several ranks: the KL from the head, the schedule as in _minibatch
+            with torch.no_grad():
+                kl_mean = out[3].clone()
+                if world > 1:
+                    D.all_reduce(kl_mean, op=dist.ReduceOp.SUM)
+                    kl_mean /= world
+                if self._lr_t is not None:
+                    lr = self._lr_t
+                    up = kl_mean > self.desired_kl * 2.0
+                    down = (kl_mean > 0.0) & (kl_mean < self.desired_kl / 2.0)
+                    self._lr_t.copy_(torch.where(up, torch.clamp(lr / 1.5, min=1e-5),
+                                                 torch.where(down, torch.clamp(lr * 1.5, max=1e-2), lr)))
+                else:
+                    k = kl_mean.item()
+                    if k > self.desired_kl * 2.0:
+                        self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+                    elif 0.0 < k < self.desired_kl / 2.0:
+                        self.learning_rate = min(1e-2, self.learning_rate * 1.5)
+                    for g in self.optimizer.param_groups:
+                        g["lr"] = self.learning_rate
+        if sym is not None:
+            symmetry_loss = self._symmetry_loss(obs, aug, n_orig)
+            if sym["use_mirror_loss"]:
+                loss = loss + sym["mirror_loss_coeff"] * symmetry_loss
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self._allreduce_grads()
+        nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        self.optimizer.step()
+        if sym is not None:
+            stats += torch.stack([out[1], out[0], out[2], symmetry_loss.detach()])
+        elif head.stats_accum is None:
+            stats += torch.stack([out[1], out[0], out[2]])
 
     def _augment(self, obs, actions, idx, obs_type):
         """data_augmentation_func on the rows ``idx``.  h12env.symmetry.augment takes the index itself: gather, mirror

@@ -1,0 +1,124 @@
+"""The PPO loss head as one autograd node.
+
+``PPOHead`` takes the networks' outputs of a minibatch -- the actor's mean, the critic's value, the std parameter -- and
+returns the scalar loss ``surrogate + value_loss_coef * value_loss - entropy_coef * entropy`` of ``PPO._minibatch``
+together with ``out`` = (surrogate loss, value loss, entropy mean, KL mean, total loss).  On CUDA tensors the forward is
+one ``h12learn_ppo_head`` call (csrc/h12_ppo_head.hip: two launches), which gathers the rollout's per-sample tensors
+itself, applies the adaptive learning-rate rule and accumulates the statistics when asked to, and leaves the three
+gradients for the backward.  On CPU tensors the same node evaluates ``_minibatch``'s torch expressions and
+differentiates them with autograd, so it is bit-identical to the default path there."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+from torch.autograd.function import once_differentiable
+from torch.distributions import Normal
+
+from . import _learn
+
+STD_KINDS = {"scalar": _learn.PPO_STD_SCALAR, "log": _learn.PPO_STD_LOG}
+
+
+def fused_loss_enabled() -> bool:
+    """H12_PPO_HEAD_FUSED=1: ppo.PPO computes the loss head with PPOHead."""
+    import os
+
+    return os.environ.get("H12_PPO_HEAD_FUSED", "0") == "1"
+
+
+@dataclass
+class HeadInputs:
+    """What the head reads besides the networks' outputs.  The rollout tensors are the storage's flattened tensors
+    (n_src rows) and ``idx`` the minibatch's rows of them; ``actions`` is such a tensor too, or, with ``actions_direct``,
+    the [m][A] actions already gathered (and mirrored).  m is idx.shape[0], or twice that under data augmentation."""
+    idx: torch.Tensor
+    old_log_prob: torch.Tensor
+    advantages: torch.Tensor
+    returns: torch.Tensor
+    target_values: torch.Tensor
+    old_mu: torch.Tensor
+    old_sigma: torch.Tensor
+    actions: torch.Tensor
+    actions_direct: bool
+    std_kind: str
+    clip_param: float
+    value_loss_coef: float
+    entropy_coef: float
+    use_clipped_value_loss: bool
+    lr: torch.Tensor | None = None  # CUDA only: the device scalar the fold's schedule rewrites
+    desired_kl: float | None = None
+    stats_accum: torch.Tensor | None = None  # CUDA only: value loss, surrogate, entropy are added to its first three
+
+
+def torch_head(mean, value, std_param, h: HeadInputs):
+    """``PPO._minibatch``'s expressions, operation for operation: (loss, out)."""
+    idx = h.idx
+    n_orig = idx.shape[0]
+    aug = mean.shape[0] != n_orig
+    actions = h.actions if h.actions_direct else h.actions[idx]
+    target_values = h.target_values[idx]
+    advantages = h.advantages[idx]
+    returns = h.returns[idx]
+    old_log_prob = h.old_log_prob[idx]
+    old_mu, old_sigma = h.old_mu[idx], h.old_sigma[idx]
+    if aug:
+        old_log_prob, target_values, advantages, returns = (torch.cat([t, t]) for t in
+                                                            (old_log_prob, target_values, advantages, returns))
+    s = std_param if h.std_kind == "scalar" else torch.exp(std_param)
+    dist = Normal(mean, s.expand_as(mean))
+    log_prob = dist.log_prob(actions).sum(dim=-1)
+    mu, sigma, entropy = dist.mean, dist.stddev, dist.entropy().sum(dim=-1)
+    if aug:
+        mu, sigma, entropy = mu[:n_orig], sigma[:n_orig], entropy[:n_orig]
+    with torch.no_grad():
+        kl = torch.sum(torch.log(sigma / old_sigma + 1e-5)
+                       + (old_sigma.square() + (old_mu - mu).square()) / (2.0 * sigma.square()) - 0.5, dim=-1)
+        kl_mean = kl.mean()
+    ratio = torch.exp(log_prob - old_log_prob.squeeze(-1))
+    adv = advantages.squeeze(-1)
+    surrogate = -adv * ratio
+    surrogate_clipped = -adv * torch.clamp(ratio, 1.0 - h.clip_param, 1.0 + h.clip_param)
+    surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
+    if h.use_clipped_value_loss:
+        v_clipped = target_values + (value - target_values).clamp(-h.clip_param, h.clip_param)
+        value_loss = torch.max((value - returns).square(), (v_clipped - returns).square()).mean()
+    else:
+        value_loss = (returns - value).square().mean()
+    entropy_mean = entropy.mean()
+    loss = surrogate_loss + h.value_loss_coef * value_loss - h.entropy_coef * entropy_mean
+    out = torch.stack([surrogate_loss.detach(), value_loss.detach(), entropy_mean.detach(), kl_mean, loss.detach()])
+    return loss, out
+
+
+class PPOHead(torch.autograd.Function):
+    """(loss, out) = PPOHead.apply(mean [m][A], value [m][1], std_param [A], HeadInputs).  ``out`` carries no
+    gradient; the backward returns the three gradients the forward computed, scaled by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, mean, value, std_param, h: HeadInputs):
+        if mean.is_cuda:
+            n = h.idx.shape[0]
+            flat = lambda t: t.reshape(-1)  # noqa: E731  ([n_src][1] storage columns; contiguous views)
+            d_mean, d_value, d_param, out = _learn.ppo_head(
+                mean, value, std_param, STD_KINDS[h.std_kind], h.idx, n, flat(h.old_log_prob), flat(h.advantages),
+                flat(h.returns), flat(h.target_values), h.old_mu, h.old_sigma, h.actions, h.actions_direct,
+                h.clip_param, h.value_loss_coef, h.entropy_coef, h.use_clipped_value_loss, lr=h.lr,
+                desired_kl=h.desired_kl, stats_accum=h.stats_accum)
+            loss = out[4].clone()
+            d_value = d_value.view_as(value)
+        else:
+            leaves = [t.detach().requires_grad_(True) for t in (mean, value, std_param)]
+            with torch.enable_grad():
+                loss, out = torch_head(*leaves, h)
+                d_mean, d_value, d_param = torch.autograd.grad(loss, leaves)
+            loss = loss.detach()
+        ctx.save_for_backward(d_mean, d_value, d_param)
+        ctx.mark_non_differentiable(out)
+        return loss, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_out):
+        d_mean, d_value, d_param = ctx.saved_tensors
+        return g * d_mean, g * d_value, g * d_param, None

@@ -58,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_learner", action="store_true", default=False,
                     help="the PPO update's actor and critic on the fused HIP forward / backward "
                          "(h12env.policy.TrainableFusedMLP; agent.algorithm.fused_learner=true works too)")
+    ap.add_argument("--fused_loss", action="store_true", default=False,
+                    help="the PPO update's loss head (gathers, losses, gradients, KL schedule) as one fused HIP call "
+                         "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
     AppLauncher.add_app_launcher_args(ap)
     return ap
 
@@ -90,6 +93,8 @@ def apply_cli(agent_cfg, env_cfg, args):
             s.mirror_loss_coeff = args.mirror_loss_coeff
     if getattr(args, "fused_learner", False):
         agent_cfg.algorithm.fused_learner = True
+    if getattr(args, "fused_loss", False):
+        agent_cfg.algorithm.fused_loss = True
     if getattr(args, "privileged_critic", False):
         from h12env.cfg import enable_privileged_critic
 

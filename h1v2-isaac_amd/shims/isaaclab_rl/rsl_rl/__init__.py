@@ -50,6 +50,8 @@ class RslRlPpoAlgorithmCfg:
     rnd_cfg: dict | None = None
     # h12env.ppo extension: actor and critic of the update on the fused HIP forward / backward (None: H12_LEARNER_FUSED)
     fused_learner: bool | None = None
+    # h12env.ppo extension: the update's loss head as one HIP call, h12env.ppo_head.PPOHead (None: H12_PPO_HEAD_FUSED)
+    fused_loss: bool | None = None
 
 
 @dataclass

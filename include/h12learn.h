@@ -1,10 +1,11 @@
 /* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
- * csrc/h12_policy_train.hip).
+ * csrc/h12_policy_train.hip, csrc/h12_ppo_head.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
  * further down, is the policy's forward itself (h12env/policy.py): normaliser and every layer in one launch.  The
- * rsl_rl-style PPO (h12env/ppo.py) uses h12learn_mirror_rows for its mirror-symmetry augmentation.
+ * rsl_rl-style PPO (h12env/ppo.py) uses h12learn_mirror_rows for its mirror-symmetry augmentation and, opt-in,
+ * h12learn_ppo_head for its loss head (at the end of this header).
  *
  * Every compute entry point
  *   - takes raw device pointers and a HIP stream,
@@ -160,6 +161,103 @@ size_t h12learn_mlp_backward_workspace_bytes(const h12learn_mlp_desc* desc, long
 int h12learn_mlp_backward(const h12learn_mlp_desc* desc, const float* packed_t, const float* dy,
                           const float* const* h, long long n, float* const* dz, float* const* db, float* dx,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fused PPO loss head (csrc/h12_ppo_head.hip): everything PPO._minibatch (h12env/ppo.py) computes between the
+ * networks' outputs and loss.backward(), in two launches: the minibatch gathers of the per-sample tensors, the Gaussian
+ * log-probability and entropy, the KL of the adaptive schedule, the clipped surrogate, the (clipped) value loss, the
+ * weighted sum, and the gradients of
+ *     loss = surrogate + value_loss_coef * value_loss - entropy_coef * entropy
+ * with respect to the actor's mean, the critic's value and the std parameter, the 1/m and 1/B means folded in.
+ *
+ * Rows.  m rows of network outputs; B = m (plain) or B = m / 2 (data augmentation: rows [B, 2B) are the mirrored
+ * samples).  Row r reads the rollout's per-sample tensors at source row k = idx[r < B ? r : r - B] (idx null: k is that
+ * row number itself, n_src >= B); an entry outside [0, n_src) is clamped into it, so nothing outside the sources is
+ * read.  actions is [n_src][A] read at row k, or, with actions_direct != 0, [m][A] read at row r (the augmented
+ * actions arrive gathered and mirrored).  The KL mean and the entropy mean run over rows [0, B).
+ *
+ * Per row, with sigma[a] = std_param[a] (H12LEARN_PPO_STD_SCALAR) or exp(std_param[a]) (H12LEARN_PPO_STD_LOG), in fp32:
+ *     log_prob = sum_a  -(actions - mean)^2 / (2 sigma^2) - log(sigma) - log(sqrt(2 pi))
+ *     ratio    = exp(log_prob - old_log_prob)
+ *     s1 = -adv * ratio,  s2 = -adv * clamp(ratio, lo, hi),  lo = 1 - clip_param, hi = 1 + clip_param
+ *     surrogate row = max(s1, s2)
+ *     e1 = value - returns,  e2 = (target + clamp(value - target, -clip_param, clip_param)) - returns
+ *     value row = max(e1^2, e2^2)                (use_clipped_value_loss == 0: (returns - value)^2)
+ *     kl row (r < B) = sum_a  log(sigma / old_sigma + 1e-5) + (old_sigma^2 + (old_mu - mean)^2) / (2 sigma^2) - 0.5
+ *     entropy row = sum_a  0.5 + 0.5 log(2 pi) + log(sigma)       (the same for every row)
+ * The bounds lo, hi, +-clip_param and the two coefficients are formed in double and narrowed once, as torch narrows the
+ * Python scalars.
+ *
+ * Tie / boundary rule: what torch autograd gives for that expression.  clamp passes the gradient on its CLOSED
+ * interval; max(x, y) gives x the weight [x > y] + [x == y] / 2 and y the weight [x < y] + [x == y] / 2.  Hence
+ *     d surrogate row / d ratio = -adv * (w1 + inside * w2),   inside = lo <= ratio <= hi,
+ *         w1 = [s1 > s2] + [s1 == s2] / 2,  w2 = [s1 < s2] + [s1 == s2] / 2:
+ *       inside the clip range (boundaries included) s1 and s2 are the same number, the halves add up: -adv, the full
+ *       gradient; outside it the clamp passes nothing: -adv where the unclipped term is the larger, 0 where the clipped
+ *       one is, -adv / 2 on an exact tie (adv == 0);
+ *     d value row / d value = 2 e1 v1 + inside_v * 2 e2 v2,   inside_v = -clip_param <= value - target <= clip_param,
+ *         v1, v2 the weights of e1^2 against e2^2 as above (inside the range e2 is e1 up to the rounding of
+ *         target + (value - target), so either operand can be the larger and both carry the gradient).
+ * The comparisons are made on separately rounded fp32 operations (no contraction), the ones torch makes.
+ *
+ * Outputs: d_mean [m][A], d_value [m], d_param [A] (the gradient of std, or of log_std), out[5] = surrogate loss, value
+ * loss, entropy mean, KL mean, total loss.  Optional, in the second launch after the KL mean is known:
+ *   lr           not null: rsl_rl's adaptive schedule on the device scalar, in place: lr / 1.5 (floor 1e-5) when
+ *                kl > 2 desired_kl; lr * 1.5 (ceiling 1e-2) when 0 < kl < desired_kl / 2; unchanged otherwise.
+ *   stats_accum  not null: stats_accum[0..2] += value loss, surrogate loss, entropy mean.
+ *
+ * Reductions without atomics: the row kernel writes, per block of h12learn_ppo_head_rows() rows, the partial sums of
+ * the surrogate, value and KL rows and of d_param to the workspace (rows in row order), the fold adds the blocks in
+ * block-index order: every output is bitwise reproducible from run to run.  The terms are fp32, the accumulators and
+ * the partial sums fp64, so a sum carries the rounding of its terms only.  The workspace needs no initialisation.
+ * Inputs are assumed finite (the library's device code is built with -ffinite-math-only). */
+#define H12LEARN_PPO_STD_SCALAR 0
+#define H12LEARN_PPO_STD_LOG 1
+
+typedef struct h12learn_ppo_head_args {
+  long long m;     /* rows of mean / value */
+  long long B;     /* minibatch rows: m, or m / 2 under data augmentation */
+  long long n_src; /* rows of the rollout tensors */
+  int A;           /* actions, 1 .. h12learn_ppo_head_max_actions() */
+  int std_kind;    /* H12LEARN_PPO_STD_* */
+  int actions_direct;
+  int use_clipped_value_loss;
+  const float* mean;      /* [m][A] */
+  const float* value;     /* [m] */
+  const float* std_param; /* [A] */
+  const long long* idx;   /* [B] or null */
+  const float* old_log_prob;  /* [n_src] */
+  const float* advantages;    /* [n_src] */
+  const float* returns;       /* [n_src] */
+  const float* target_values; /* [n_src] */
+  const float* old_mu;        /* [n_src][A] */
+  const float* old_sigma;     /* [n_src][A] */
+  const float* actions;       /* [n_src][A], or [m][A] with actions_direct */
+  double clip_param;
+  double value_loss_coef;
+  double entropy_coef;
+  double desired_kl; /* read only when lr is not null; must then be > 0 */
+  float* d_mean;     /* [m][A] */
+  float* d_value;    /* [m] */
+  float* d_param;    /* [A] */
+  float* out;        /* [5] */
+  float* lr;          /* device scalar, or null */
+  float* stats_accum; /* [3], or null */
+  void* workspace;    /* 8-byte aligned, h12learn_ppo_head_workspace_bytes(m, A) */
+  size_t workspace_bytes;
+} h12learn_ppo_head_args;
+
+/* Rows of a block of the row kernel (the row tile R); a query so tests can place m at R-1, R, R+1, 2R+1. */
+int h12learn_ppo_head_rows(void);
+
+/* The largest supported number of actions (>= 32). */
+int h12learn_ppo_head_max_actions(void);
+
+/* Bytes of workspace for m rows of A actions: ceil(m / R) blocks of 3 + A fp64 partial sums.  0 with
+ * h12learn_last_error set when m or A is invalid. */
+size_t h12learn_ppo_head_workspace_bytes(long long m, int A);
+
+/* Two launches (row kernel, fold).  No output may overlap an input. */
+int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream);
 
 const char* h12learn_last_error(void);
 

@@ -18,6 +18,8 @@
 //
 // No atomics, no counters, nothing to initialise: every output is a fixed-order sum.  The summed terms are fp32, the
 // accumulators and the partials fp64, so a sum carries the rounding of its terms only.
+//
+// The CleanRL trainer's head (h12learn_cleanrl_head) follows the PPO head's kernels below, on the same helpers.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -57,8 +59,8 @@ struct HeadScalars {
     }                                                                                       \
   } while (0)
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
+template <int G, typename T = float>
+__device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
   for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
   return v;
@@ -68,6 +70,59 @@ __device__ __forceinline__ float group_sum(float v) {
 __device__ __forceinline__ void max_weights(float x, float y, float& wx, float& wy) {
   wx = x > y ? 1.0f : (x == y ? 0.5f : 0.0f);
   wy = x < y ? 1.0f : (x == y ? 0.5f : 0.0f);
+}
+
+// The two sums below are the loops of ppo_head_rows_kernel and ppo_head_fold_kernel as functions, for the CleanRL head's
+// kernels.  Those two kernels keep their loops inline: routed through these functions they compile to other code
+// (block order and branches), and their code object is to stay what it was.
+//
+// row-order sum of one column of an LDS array of HEAD_ROWS rows, `stride` floats apart (fp64 accumulator: the sum then
+// carries the rounding of its fp32 terms only); SUM_BATCH reads in flight ahead of the dependent adds
+__device__ __forceinline__ double rows_sum(const float* col, int stride) {
+  double acc = 0.0;
+  for (int r = 0; r < HEAD_ROWS; r += SUM_BATCH) {
+    float v[SUM_BATCH];
+#pragma unroll
+    for (int j = 0; j < SUM_BATCH; ++j) v[j] = col[(r + j) * stride];
+#pragma unroll
+    for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
+  }
+  return acc;
+}
+
+// the fold's sums: `blocks` partials of P quantities each are staged through s_buf (FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)
+// doubles of LDS) in chunks (coalesced, all loads in flight); thread j < P returns quantity j added in block-index order
+__device__ __forceinline__ double fold_sum(const double* partial, int blocks, int P, int tid, double* s_buf) {
+  double acc = 0.0;
+  for (int c0 = 0; c0 < blocks; c0 += FOLD_CHUNK) {
+    const int cnt = blocks - c0 < FOLD_CHUNK ? blocks - c0 : FOLD_CHUNK;
+    const int total = cnt * P;
+    const double* src = partial + (size_t)c0 * (size_t)P;
+    double stage[FOLD_PER_THREAD];  // every load of the chunk issued before the first LDS store
+#pragma unroll
+    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
+      const int i = tid + j * FOLD_THREADS;
+      stage[j] = i < total ? src[i] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
+      const int i = tid + j * FOLD_THREADS;
+      if (i < total) s_buf[i] = stage[j];
+    }
+    __syncthreads();
+    if (tid < P) {
+      // block-index order; SUM_BATCH reads in flight ahead of the dependent adds (a tail adds +0.0: no change)
+      for (int b = 0; b < cnt; b += SUM_BATCH) {
+        double v[SUM_BATCH];
+#pragma unroll
+        for (int j = 0; j < SUM_BATCH; ++j) v[j] = b + j < cnt ? s_buf[(b + j) * P + tid] : 0.0;
+#pragma unroll
+        for (int j = 0; j < SUM_BATCH; ++j) acc += v[j];
+      }
+    }
+    __syncthreads();  // the buffer is reused by the next chunk
+  }
+  return acc;
 }
 
 template <int G>
@@ -286,6 +341,253 @@ __global__ __launch_bounds__(FOLD_THREADS) void ppo_head_fold_kernel(h12learn_pp
   }
 }
 
+// ---- the CleanRL head (include/h12learn.h, h12learn_cleanrl_head): the same rows-in-lane-groups layout, butterflies,
+// fp64 block partials and in-order fold, with the per-minibatch advantage normalisation in front of the rows:
+//
+//   1. cleanrl_adv_kernel        one wave per block of HEAD_ROWS rows, a row per lane: the gathered advantages' two-pass
+//      (count, mean, M2) in fp64, the sums butterflies over the wave.
+//   2. cleanrl_head_rows_kernel<G>   every block first merges the advantage partials of all blocks itself, in block-index
+//      order: thread j stages partial j and its two merge coefficients (the counts in front of block j are j HEAD_ROWS, so
+//      the divisions are off the dependent chain), thread 0 runs Chan's update over them.  Then the rows, as above.
+//   3. cleanrl_head_fold_kernel  the in-order fold, the entropy, the total, the statistics, d_logstd.
+constexpr int CLEAN_SC = 3;    // per-row scalars that are summed: pg, v, clip indicator
+constexpr int CLEAN_ADV = 3;   // a block's advantage partial: count, mean, M2
+constexpr int MERGE_CHUNK = HEAD_WAVES * 64;  // advantage partials staged in LDS at a time
+static_assert(CLEAN_SC <= HEAD_SC, "fold_sum's staging buffer is sized for HEAD_SC + HEAD_MAX_A quantities");
+
+struct CleanScalars {
+  float lo, hi;  // 1 -+ clip_coef
+  float clip;
+  float vcoef, ecoef;
+  float veps;
+};
+
+__global__ __launch_bounds__(64) void cleanrl_adv_kernel(h12learn_cleanrl_head_args p, double* apart) {
+#pragma clang fp contract(off)
+  static_assert(HEAD_ROWS == 64, "one wave per block, a row per lane");
+  const int lane = threadIdx.x;
+  const long long first = (long long)blockIdx.x * HEAD_ROWS;
+  const long long left = p.m - first;
+  const int n = left < HEAD_ROWS ? (int)left : HEAD_ROWS;
+  const bool live = lane < n;
+  const long long rr = live ? first + lane : p.m - 1;
+  long long k = p.idx ? p.idx[rr] : rr;
+  k = k < 0 ? 0 : (k < p.n_src ? k : p.n_src - 1);
+  const double x = (double)p.advantages[k];
+  const double mean = group_sum<64, double>(live ? x : 0.0) / (double)n;
+  const double d = live ? x - mean : 0.0;
+  const double m2 = group_sum<64, double>(d * d);
+  if (lane == 0) {
+    double* out = apart + (size_t)blockIdx.x * CLEAN_ADV;
+    out[0] = (double)n;
+    out[1] = mean;
+    out[2] = m2;
+  }
+}
+
+// Chan's merge of the blocks' advantage partials in block-index order, by every thread of a block of MERGE_CHUNK threads
+// together: s_adv[0] = the minibatch's mean, s_adv[1] = its std (correction 1) + 1e-8, both narrowed once.  Thread j
+// stages partial j and its two coefficients (the count in front of block j is j HEAD_ROWS: the divisions are off the
+// dependent chain), thread 0 runs the chain.  Ends on a barrier.
+__device__ __forceinline__ void merge_adv(const double* apart, int blocks, long long m, int tid,
+                                          double (*s_mg)[4], float* s_adv) {
+#pragma clang fp contract(off)
+  double mean = 0.0, m2 = 0.0;  // thread 0's running merge
+  for (int c0 = 0; c0 < blocks; c0 += MERGE_CHUNK) {
+    const int cnt = blocks - c0 < MERGE_CHUNK ? blocks - c0 : MERGE_CHUNK;
+    if (tid < cnt) {
+      const double* q = apart + (size_t)(c0 + tid) * CLEAN_ADV;
+      const double nb = q[0], na = (double)(c0 + tid) * (double)HEAD_ROWS;  // every block before the last is full
+      const double n = na + nb;
+      s_mg[tid][0] = q[1];
+      s_mg[tid][1] = q[2];
+      s_mg[tid][2] = nb / n;
+      s_mg[tid][3] = na * nb / n;
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll 4
+      for (int j = 0; j < cnt; ++j) {  // Chan: mean += delta nb / n;  M2 += M2_b + delta^2 na nb / n
+        const double delta = s_mg[j][0] - mean;
+        mean = mean + delta * s_mg[j][2];
+        m2 = m2 + (s_mg[j][1] + delta * delta * s_mg[j][3]);
+      }
+    }
+    __syncthreads();  // the buffer is reused by the next chunk
+  }
+  if (tid == 0) {
+    s_adv[0] = (float)mean;
+    s_adv[1] = (float)sqrt(m2 / (double)(m - 1)) + 1.0e-8f;  // torch.std: correction 1
+  }
+  __syncthreads();
+}
+
+template <int G>
+__global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12learn_cleanrl_head_args p,
+                                                                            CleanScalars sc, const double* apart,
+                                                                            double* partial, int blocks) {
+#pragma clang fp contract(off)
+  constexpr int GROUPS = 64 / G;
+  constexpr int PASS_ROWS = HEAD_WAVES * GROUPS;
+  constexpr int PASSES = HEAD_ROWS / PASS_ROWS;
+  static_assert(PASSES % HEAD_UNROLL == 0, "the passes are taken HEAD_UNROLL at a time");
+  static_assert(HEAD_ROWS % SUM_BATCH == 0, "the row sums read SUM_BATCH rows at a time");
+  __shared__ float s_dp[HEAD_ROWS][G];
+  __shared__ float s_sc[HEAD_ROWS][CLEAN_SC + 1];
+  __shared__ double s_mg[MERGE_CHUNK][4];
+  __shared__ float s_adv[2];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int a = lane & (G - 1), grp = lane / G;
+  const int A = p.A;
+  const bool col = a < A;
+  const int ac = col ? a : A - 1;  // lanes past A re-read the last column and contribute nothing
+  const long long m = p.m;
+  const float inv_m = 1.0f / (float)m;
+
+  const float logstd = p.logstd[ac];
+  const float sigma = expf(logstd);
+  const float two_var = 2.0f * (sigma * sigma);
+  const float inv_sigma = 1.0f / sigma;
+  const float inv_var = inv_sigma * inv_sigma;
+  // value_rms (update=False): (value - running_mean) / sqrt(running_var + epsilon)
+  const float vmean = *p.value_mean;
+  const float vsd = sqrtf(*p.value_var + sc.veps);
+
+  float adv_mean = 0.0f, adv_den = 1.0f;
+  if (p.norm_adv) {
+    merge_adv(apart, blocks, m, tid, s_mg, s_adv);
+    adv_mean = s_adv[0];
+    adv_den = s_adv[1];
+  }
+
+  const long long block_row = (long long)blockIdx.x * HEAD_ROWS;
+  for (int p0 = 0; p0 < PASSES; p0 += HEAD_UNROLL) {
+    long long rr[HEAD_UNROLL], k[HEAD_UNROLL];
+    int rl[HEAD_UNROLL];
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 1: the indices
+      rl[i] = (p0 + i) * PASS_ROWS + w * GROUPS + grp;
+      const long long r = block_row + rl[i];
+      rr[i] = r < m ? r : m - 1;  // rows past m re-read row m - 1 and store nothing
+      k[i] = p.idx ? p.idx[rr[i]] : rr[i];
+    }
+    float mu[HEAD_UNROLL], act[HEAD_UNROLL];
+    float olp[HEAD_UNROLL], adv[HEAD_UNROLL], ret[HEAD_UNROLL], vn[HEAD_UNROLL], val[HEAD_UNROLL];
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 2: everything else
+      k[i] = k[i] < 0 ? 0 : (k[i] < p.n_src ? k[i] : p.n_src - 1);
+      mu[i] = p.mean[(size_t)rr[i] * (size_t)A + ac];
+      act[i] = p.actions[(size_t)k[i] * (size_t)A + ac];
+      olp[i] = adv[i] = ret[i] = vn[i] = val[i] = 0.0f;
+      if (a == 0) {
+        olp[i] = p.old_log_prob[k[i]];
+        adv[i] = p.advantages[k[i]];
+        ret[i] = p.returns_n[k[i]];
+        vn[i] = p.values_n[k[i]];
+        val[i] = p.value[rr[i]];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < HEAD_UNROLL; ++i) {
+      const bool live = block_row + rl[i] < m;
+      const float d = act[i] - mu[i];
+      const float dd = d * d;
+      const float lp_a = -dd / two_var - logstd - LOG_SQRT_2PI;
+      const float log_prob = group_sum<G>(col ? lp_a : 0.0f);
+      float g_lp = 0.0f;
+      if (a == 0) {
+        const float ad = p.norm_adv ? (adv[i] - adv_mean) / adv_den : adv[i];
+        const float ratio = expf(log_prob - olp[i]);
+        const float s1 = -ad * ratio;
+        const float s2 = -ad * fminf(fmaxf(ratio, sc.lo), sc.hi);
+        const bool inside = ratio >= sc.lo && ratio <= sc.hi;
+        float w1, w2;
+        max_weights(s1, s2, w1, w2);
+        g_lp = inv_m * (-ad * (w1 + (inside ? w2 : 0.0f))) * ratio;
+        const float nv = (val[i] - vmean) / vsd;
+        float vl, dv;
+        if (p.clip_vloss) {
+          const float dvt = nv - vn[i];
+          const float vc = vn[i] + fminf(fmaxf(dvt, -sc.clip), sc.clip);
+          const bool inside_v = dvt >= -sc.clip && dvt <= sc.clip;
+          const float e1 = nv - ret[i], e2 = vc - ret[i];
+          const float q1 = e1 * e1, q2 = e2 * e2;
+          float v1, v2;
+          max_weights(q1, q2, v1, v2);
+          vl = fmaxf(q1, q2);
+          dv = v1 * (2.0f * e1) + (inside_v ? v2 * (2.0f * e2) : 0.0f);
+        } else {
+          const float e = nv - ret[i];
+          vl = e * e;
+          dv = 2.0f * e;
+        }
+        // d loss / d v row = vf_coef * 0.5 / m; d nv / d value = 1 / sqrt(var + eps)
+        if (live) p.d_value[rr[i]] = ((sc.vcoef * 0.5f * inv_m) * dv) / vsd;
+        s_sc[rl[i]][0] = live ? fmaxf(s1, s2) : 0.0f;
+        s_sc[rl[i]][1] = live ? vl : 0.0f;
+        s_sc[rl[i]][2] = live && fabsf(ratio - 1.0f) > sc.clip ? 1.0f : 0.0f;
+      }
+      g_lp = __shfl(g_lp, 0, G);
+      if (live && col) p.d_mean[(size_t)rr[i] * (size_t)A + a] = g_lp * (d * inv_var);
+      // d log_prob / d logstd = (actions - mean)^2 / sigma^2 - 1
+      s_dp[rl[i]][a] = live && col ? g_lp * (dd * inv_var - 1.0f) : 0.0f;
+    }
+  }
+  __syncthreads();
+  // row-order sums: threads [0, A) of wave 0 take d_logstd's columns, threads [64, 64 + CLEAN_SC) the scalars
+  double* out = partial + (size_t)blockIdx.x * (size_t)(CLEAN_SC + A);
+  if (tid < A) {
+    out[CLEAN_SC + tid] = rows_sum(&s_dp[0][tid], G);
+  } else if (tid >= 64 && tid < 64 + CLEAN_SC) {
+    const int q = tid - 64;
+    out[q] = rows_sum(&s_sc[0][q], CLEAN_SC + 1);
+  }
+}
+
+__global__ __launch_bounds__(FOLD_THREADS) void cleanrl_head_fold_kernel(h12learn_cleanrl_head_args p, CleanScalars sc,
+                                                                          const double* partial, int blocks) {
+#pragma clang fp contract(off)
+  __shared__ double s_buf[FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)];
+  __shared__ double s_fin[CLEAN_SC + HEAD_MAX_A];
+  __shared__ double s_ent[HEAD_MAX_A];
+  const int tid = threadIdx.x;
+  const int P = CLEAN_SC + p.A;
+  // issued before the partials are touched, so these latencies overlap the sums
+  const float logstd = tid >= CLEAN_SC && tid < P ? p.logstd[tid - CLEAN_SC] : 0.0f;
+  float st[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (tid == 0 && p.stats_accum) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) st[j] = p.stats_accum[j];
+  }
+  const double acc = fold_sum(partial, blocks, P, tid, s_buf);
+  if (tid < P) s_fin[tid] = acc;
+  if (tid >= CLEAN_SC && tid < P) {
+    // the entropy is sum_a logstd[a] + const, the same for every row: d (-ent_coef * entropy) / d logstd[a] = -ent_coef
+    p.d_logstd[tid - CLEAN_SC] = (float)(acc - (double)sc.ecoef);
+    s_ent[tid - CLEAN_SC] = (0.5 + LOG_SQRT_2PI_D) + (double)logstd;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double ent_sum = 0.0;
+    for (int a = 0; a < p.A; ++a) ent_sum += s_ent[a];
+    const double pg_d = s_fin[0] / (double)p.m, v_d = 0.5 * (s_fin[1] / (double)p.m);
+    float o[5];
+    o[0] = (float)pg_d;
+    o[1] = (float)ent_sum;
+    o[2] = (float)v_d;
+    o[3] = (float)(pg_d - (double)sc.ecoef * ent_sum + (double)sc.vcoef * v_d);
+    o[4] = (float)(s_fin[2] / (double)p.m);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) p.out[j] = o[j];
+    if (p.stats_accum) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) p.stats_accum[j] = st[j] + o[j];
+    }
+  }
+}
+
 long long head_blocks(long long m) { return (m + HEAD_ROWS - 1) / HEAD_ROWS; }
 
 }  // namespace
@@ -356,6 +658,79 @@ int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream) {
     hipLaunchKernelGGL(ppo_head_rows_kernel<32>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc, partial);
   HEAD_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(ppo_head_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, s, p, sc, (const double*)partial,
+                     (int)blocks);
+  HEAD_HIP_TRY(hipGetLastError());
+  return H12LEARN_OK;
+}
+
+int h12learn_cleanrl_head_rows(void) { return HEAD_ROWS; }
+
+size_t h12learn_cleanrl_head_workspace_bytes(long long m, int A) {
+  if (m < 1) {
+    h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head_workspace_bytes: m = %lld (must be >= 1)", m);
+    return 0;
+  }
+  if (A < 1 || A > HEAD_MAX_A) {
+    h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head_workspace_bytes: A = %d (1 .. %d)", A, HEAD_MAX_A);
+    return 0;
+  }
+  return (size_t)head_blocks(m) * (size_t)(CLEAN_ADV + CLEAN_SC + A) * sizeof(double);
+}
+
+int h12learn_cleanrl_head(const h12learn_cleanrl_head_args* args, void* stream) {
+  if (!args) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: args is null");
+  const h12learn_cleanrl_head_args& p = *args;
+  if (p.m < 1) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld (must be >= 1)", p.m);
+  if (p.norm_adv && p.m < 2)
+    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld with norm_adv (the std of one advantage is NaN)", p.m);
+  if (p.A < 1 || p.A > HEAD_MAX_A)
+    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: A = %d (1 .. %d)", p.A, HEAD_MAX_A);
+  if (p.n_src < 1) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: n_src = %lld (must be >= 1)", p.n_src);
+  if (!p.idx && p.m > p.n_src)
+    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld rows of sources of n_src = %lld without idx", p.m,
+                          p.n_src);
+  const struct {
+    const void* ptr;
+    const char* name;
+  } required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.logstd, "logstd"}, {p.old_log_prob, "old_log_prob"},
+                  {p.advantages, "advantages"}, {p.returns_n, "returns_n"}, {p.values_n, "values_n"},
+                  {p.actions, "actions"}, {p.value_mean, "value_mean"}, {p.value_var, "value_var"},
+                  {p.d_mean, "d_mean"}, {p.d_value, "d_value"}, {p.d_logstd, "d_logstd"}, {p.out, "out"},
+                  {p.workspace, "workspace"}};
+  for (const auto& q : required)
+    if (!q.ptr) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: %s is null", q.name);
+  if (!(p.clip_coef >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: clip_coef = %g (must be >= 0)", p.clip_coef);
+  if (!(p.value_eps >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: value_eps = %g (must be >= 0)", p.value_eps);
+  const size_t need = h12learn_cleanrl_head_workspace_bytes(p.m, p.A);
+  if (p.workspace_bytes < need)
+    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: workspace_bytes = %zu, %zu needed", p.workspace_bytes, need);
+  if (((uintptr_t)p.workspace & 7) != 0)
+    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: workspace is not 8-byte aligned");
+  const long long blocks = head_blocks(p.m);
+  if (blocks > 0x7fffffffLL) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld exceeds the grid", p.m);
+
+  CleanScalars sc;
+  sc.lo = (float)(1.0 - p.clip_coef);
+  sc.hi = (float)(1.0 + p.clip_coef);
+  sc.clip = (float)p.clip_coef;
+  sc.vcoef = (float)p.vf_coef;
+  sc.ecoef = (float)p.ent_coef;
+  sc.veps = (float)p.value_eps;
+  hipStream_t s = (hipStream_t)stream;
+  double* apart = (double*)p.workspace;
+  double* partial = apart + (size_t)blocks * CLEAN_ADV;
+  if (p.norm_adv) {
+    hipLaunchKernelGGL(cleanrl_adv_kernel, dim3((unsigned)blocks), dim3(64), 0, s, p, apart);
+    HEAD_HIP_TRY(hipGetLastError());
+  }
+  if (p.A <= 16)
+    hipLaunchKernelGGL(cleanrl_head_rows_kernel<16>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc,
+                       (const double*)apart, partial, (int)blocks);
+  else
+    hipLaunchKernelGGL(cleanrl_head_rows_kernel<32>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc,
+                       (const double*)apart, partial, (int)blocks);
+  HEAD_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(cleanrl_head_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, s, p, sc, (const double*)partial,
                      (int)blocks);
   HEAD_HIP_TRY(hipGetLastError());
   return H12LEARN_OK;

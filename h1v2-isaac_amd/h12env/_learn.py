@@ -16,7 +16,8 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_mlp_train_max_width", "h12learn_mlp_packed_t_bytes", "h12learn_mlp_pack_t",
                  "h12learn_mlp_forward_train", "h12learn_mlp_backward_workspace_bytes", "h12learn_mlp_backward",
                  "h12learn_ppo_head_rows", "h12learn_ppo_head_max_actions", "h12learn_ppo_head_workspace_bytes",
-                 "h12learn_ppo_head", "h12learn_last_error"]
+                 "h12learn_ppo_head", "h12learn_cleanrl_head_rows", "h12learn_cleanrl_head_workspace_bytes",
+                 "h12learn_cleanrl_head", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -49,6 +50,18 @@ class PpoHeadArgs(C.Structure):
                 ("d_mean", C.c_void_p), ("d_value", C.c_void_p), ("d_param", C.c_void_p), ("out", C.c_void_p),
                 ("lr", C.c_void_p), ("stats_accum", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t)]
+
+
+class CleanRlHeadArgs(C.Structure):
+    """h12learn_cleanrl_head_args"""
+    _fields_ = [("m", C.c_longlong), ("n_src", C.c_longlong), ("A", C.c_int), ("norm_adv", C.c_int),
+                ("clip_vloss", C.c_int), ("reserved", C.c_int), ("mean", C.c_void_p), ("value", C.c_void_p),
+                ("logstd", C.c_void_p), ("idx", C.c_void_p), ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p),
+                ("returns_n", C.c_void_p), ("values_n", C.c_void_p), ("actions", C.c_void_p),
+                ("value_mean", C.c_void_p), ("value_var", C.c_void_p), ("value_eps", C.c_double),
+                ("clip_coef", C.c_double), ("ent_coef", C.c_double), ("vf_coef", C.c_double), ("d_mean", C.c_void_p),
+                ("d_value", C.c_void_p), ("d_logstd", C.c_void_p), ("out", C.c_void_p), ("stats_accum", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 _bound = None
@@ -106,6 +119,12 @@ def learn_library():
     lib.h12learn_ppo_head_workspace_bytes.restype = C.c_size_t
     lib.h12learn_ppo_head.argtypes = [C.POINTER(PpoHeadArgs), vp]
     lib.h12learn_ppo_head.restype = C.c_int
+    lib.h12learn_cleanrl_head_rows.argtypes = []
+    lib.h12learn_cleanrl_head_rows.restype = C.c_int
+    lib.h12learn_cleanrl_head_workspace_bytes.argtypes = [C.c_longlong, C.c_int]
+    lib.h12learn_cleanrl_head_workspace_bytes.restype = C.c_size_t
+    lib.h12learn_cleanrl_head.argtypes = [C.POINTER(CleanRlHeadArgs), vp]
+    lib.h12learn_cleanrl_head.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -423,3 +442,81 @@ def ppo_head(mean: torch.Tensor, value: torch.Tensor, std_param: torch.Tensor, s
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     _check(lib, lib.h12learn_ppo_head(C.byref(a), _stream(dev)), "h12learn_ppo_head")
     return d_mean, d_value, d_param, out
+
+
+# ---- fused CleanRL loss head (csrc/h12_ppo_head.hip)
+def cleanrl_head_rows() -> int:
+    return learn_library().h12learn_cleanrl_head_rows()
+
+
+_cleanrl_ws: dict = {}
+
+
+def cleanrl_head_workspace(m: int, A: int, device) -> torch.Tensor:
+    """The head's workspace for [m][A] outputs, cached per (device, m, A); it needs no initialisation and is reused by
+    every call of that shape (calls on one stream are ordered, and the head reads only what it has just written)."""
+    key = (torch.device(device), int(m), int(A))
+    ws = _cleanrl_ws.get(key)
+    if ws is None:
+        lib = learn_library()
+        nbytes = lib.h12learn_cleanrl_head_workspace_bytes(m, A)
+        if nbytes == 0:
+            _check(lib, -1, "h12learn_cleanrl_head_workspace_bytes")
+        ws = _cleanrl_ws[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def cleanrl_head(mean: torch.Tensor, value: torch.Tensor, logstd: torch.Tensor, idx, old_log_prob, advantages,
+                 returns_n, values_n, actions, value_mean: torch.Tensor, value_var: torch.Tensor, value_eps: float,
+                 clip_coef: float, ent_coef: float, vf_coef: float, norm_adv: bool, clip_vloss: bool,
+                 stats_accum: torch.Tensor | None = None, workspace: torch.Tensor | None = None):
+    """Three launches: (d_mean [m][A], d_value [m], d_logstd [A], out [5]) of the CleanRL loss head on mean [m][A],
+    value (m elements) and actor_logstd (A elements).  idx (None, or m int64 entries) selects the rows of the rollout
+    tensors (n_src rows each); value_mean / value_var are value_rms's device scalars, read by the kernel.
+    ``stats_accum`` (5 floats) is updated in place when given; ``workspace`` defaults to the cached one.
+    include/h12learn.h has the formulae."""
+    lib = learn_library()
+    _f32(mean, "mean"), _f32(value, "value"), _f32(logstd, "logstd")
+    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 1:
+        raise ValueError(f"cleanrl_head: mean {tuple(mean.shape)} is not (m >= 1, A >= 1)")
+    m, A = mean.shape
+    dev = mean.device
+    if value.numel() != m or logstd.numel() != A:
+        raise ValueError(f"cleanrl_head: value has {value.numel()} and logstd {logstd.numel()} elements for mean "
+                         f"{tuple(mean.shape)}")
+    n_src = old_log_prob.numel()
+    for name, t in (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns_n", returns_n),
+                    ("values_n", values_n)):
+        if _f32(t, name).numel() != n_src:
+            raise ValueError(f"cleanrl_head: {name} must have {n_src} elements")
+    if _f32(actions, "actions").shape != (n_src, A):
+        raise ValueError(f"cleanrl_head: actions {tuple(actions.shape)} must be ({n_src}, {A})")
+    for name, t in (("value_mean", value_mean), ("value_var", value_var)):
+        if _f32(t, name).numel() != 1:
+            raise ValueError(f"cleanrl_head: {name} must be one float32 element")
+    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
+                                and idx.shape == (m,)):
+        raise ValueError(f"cleanrl_head: idx must be a contiguous int64 CUDA tensor of {m} entries")
+    if stats_accum is not None and _f32(stats_accum, "stats_accum").numel() < 5:
+        raise ValueError("cleanrl_head: stats_accum must have at least 5 elements")
+    ws = cleanrl_head_workspace(m, A, dev) if workspace is None else workspace
+    if not (ws.is_cuda and ws.is_contiguous()):
+        raise ValueError("cleanrl_head: workspace must be a contiguous CUDA tensor")
+    d_mean = torch.empty((m, A), dtype=torch.float32, device=dev)
+    d_value = torch.empty(m, dtype=torch.float32, device=dev)
+    d_logstd = torch.empty(A, dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    a = CleanRlHeadArgs()
+    a.m, a.n_src, a.A = m, n_src, A
+    a.norm_adv, a.clip_vloss = int(bool(norm_adv)), int(bool(clip_vloss))
+    a.mean, a.value, a.logstd = mean.data_ptr(), value.data_ptr(), logstd.data_ptr()
+    a.idx = None if idx is None else idx.data_ptr()
+    a.old_log_prob, a.advantages = old_log_prob.data_ptr(), advantages.data_ptr()
+    a.returns_n, a.values_n, a.actions = returns_n.data_ptr(), values_n.data_ptr(), actions.data_ptr()
+    a.value_mean, a.value_var, a.value_eps = value_mean.data_ptr(), value_var.data_ptr(), float(value_eps)
+    a.clip_coef, a.ent_coef, a.vf_coef = float(clip_coef), float(ent_coef), float(vf_coef)
+    a.d_mean, a.d_value, a.d_logstd, a.out = d_mean.data_ptr(), d_value.data_ptr(), d_logstd.data_ptr(), out.data_ptr()
+    a.stats_accum = None if stats_accum is None else stats_accum.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _check(lib, lib.h12learn_cleanrl_head(C.byref(a), _stream(dev)), "h12learn_cleanrl_head")
+    return d_mean, d_value, d_logstd, out

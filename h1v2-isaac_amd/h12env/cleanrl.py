@@ -28,7 +28,12 @@ Deviations from the reference, all deliberate:
     it at 4096 envs turned finite observations non-finite on the MI355X, which eager it never does).  On CUDA the
     sample is ``mean + std * randn_like(mean)`` in both modes; on CPU it is ``Normal(mean, std).sample()`` and one
     ``torch.randperm(BATCH)`` per epoch, the reference's calls in the reference's order;
-  * the update stays eager;
+  * the update stays eager, unless ``fused_loss`` is on (``PPO(..., fused_loss=True)``, ``H12_CLEANRL_HEAD_FUSED=1``,
+    ``train_cleanrl.py --fused_loss``): everything from ``logratio`` to ``loss`` is then one
+    ``CleanRLHead`` node (h12learn_cleanrl_head on CUDA, the same torch expressions on CPU), the optimiser is the
+    capturable RAdam with the learning rate as a device scalar, and on CUDA a whole minibatch (gather, forwards, head,
+    backward, gradient clip, RAdam step) replays as one HIP graph per minibatch size; ``H12_PPO_GRAPH=0`` runs the
+    same minibatch eagerly, bit for bit;
   * the storage, the agent and the rollout live on the env's device (the reference picks cuda when available);
   * the running statistics are updated in place (the reference rebinds the buffers), so a graph can hold them;
   * ``PPO`` returns the trained agent (the reference returns None) and takes ``resume_path`` / ``on_step``.
@@ -361,11 +366,116 @@ def _episode_scalars(ep_infos, device) -> dict:
     return dict(zip(names, torch.stack(vals).tolist())) if vals else {}
 
 
+# ---------------------------------------------------------------------------------------------- fused update
+class _FusedUpdate:
+    """The minibatch of ``PPO(fused_loss=True)``: gather the observations, actor and critic forward, ``CleanRLHead``,
+    backward, gradient clip, optimiser step.  On CUDA the loss statistics accumulate on the device in ``stats``
+    (pg, entropy, v, total, clip fraction) and, graphed, each minibatch size replays a graph of its own, captured at its
+    first use with ``ppo.PPO._capture``'s discipline: warm-up on a side stream, then parameters, optimiser state and
+    statistics put back bit for bit.  On CPU the node evaluates the default path's expressions."""
+
+    def __init__(self, agent, optimizer, cfg, batch_size: int, device, graphed: bool):
+        self.agent, self.optimizer, self.cfg, self.device = agent, optimizer, cfg, device
+        self.cuda = device.type == "cuda"
+        self.graphed = graphed and self.cuda
+        self._graphs: dict = {}  # minibatch size -> (graph, static index buffer)
+        self.stats = torch.zeros(5, device=device)
+        self.n_minibatches = 0
+        self.clipfracs: list = []  # CPU: the default path's list
+        # static copies of what an iteration computes anew (advantages, normalised values and returns)
+        self.adv, self.values_n, self.returns_n = (torch.zeros(batch_size, device=device) for _ in range(3))
+        self.obs = self.logprobs = self.actions = None
+
+    def begin(self, b_obs, b_logprobs, b_actions, b_advantages, b_values, b_returns):
+        """An iteration's rollout: the storage's flattened tensors (static) and the three computed after collection."""
+        self.obs, self.logprobs, self.actions = b_obs, b_logprobs, b_actions
+        self.adv.copy_(b_advantages)
+        self.values_n.copy_(b_values)
+        self.returns_n.copy_(b_returns)
+        self.stats.zero_()
+        self.n_minibatches = 0
+        self.clipfracs = []
+
+    def _minibatch(self, idx):
+        from .ppo_head import CleanRLHead, CleanRLInputs
+
+        agent, c = self.agent, self.cfg
+        x = self.obs[idx]
+        h = CleanRLInputs(idx=idx, old_log_prob=self.logprobs, advantages=self.adv, returns_n=self.returns_n,
+                          values_n=self.values_n, actions=self.actions, value_rms=agent.value_rms,
+                          clip_coef=c.clip_coef, ent_coef=c.ent_coef, vf_coef=c.vf_coef, norm_adv=c.norm_adv,
+                          clip_vloss=c.clip_vloss, stats_accum=self.stats if self.cuda else None)
+        loss, out = CleanRLHead.apply(agent.actor_mean(x), agent.critic(x), agent.actor_logstd, h)
+        self.optimizer.zero_grad()
+        loss.backward()
+        nn.utils.clip_grad_norm_(agent.parameters(), c.max_grad_norm)
+        self.optimizer.step()
+        return out
+
+    def step(self, mb_inds):
+        self.n_minibatches += 1
+        if self.graphed:
+            ent = self._graphs.get(mb_inds.shape[0])
+            if ent is None:
+                ent = self._graphs[mb_inds.shape[0]] = self._capture(mb_inds.shape[0])
+            g, idx = ent
+            idx.copy_(mb_inds)
+            g.replay()
+            return
+        out = self._minibatch(mb_inds)
+        if not self.cuda:
+            self.stats[:4] += out[:4]
+            self.clipfracs.append(out[4])
+
+    def _snapshot(self):
+        params = list(self.agent.parameters())
+        st = {p: {k: v.detach().clone() for k, v in self.optimizer.state.get(p, {}).items() if torch.is_tensor(v)}
+              for p in params}
+        return [p.detach().clone() for p in params], st, self.stats.clone()
+
+    def _restore(self, snap):
+        params, st, stats = snap
+        with torch.no_grad():
+            for p, v in zip(self.agent.parameters(), params):
+                p.copy_(v)
+                for k, t in self.optimizer.state.get(p, {}).items():
+                    if torch.is_tensor(t):
+                        t.copy_(st[p][k]) if k in st[p] else t.zero_()  # lazily created by the warm-up: initial 0
+            self.stats.copy_(stats)
+
+    def _capture(self, mb: int):
+        dev = self.device
+        idx = torch.arange(mb, dtype=torch.long, device=dev)
+        snap = self._snapshot()
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._minibatch(idx)
+        torch.cuda.current_stream(dev).wait_stream(s)
+        self._restore(snap)
+        g = torch.cuda.CUDAGraph()
+        self.optimizer.zero_grad(set_to_none=True)
+        with torch.cuda.graph(g):
+            self._minibatch(idx)
+        return g, idx
+
+    def means(self, num_updates: float):
+        """(pg, entropy, v, total, clip fraction) of the iteration, on the device."""
+        if self.cuda:
+            return torch.cat([self.stats[:4] / num_updates, self.stats[4:] / max(self.n_minibatches, 1)])
+        return torch.cat([self.stats[:4] / num_updates, torch.stack(self.clipfracs).mean().reshape(1)])
+
+
 # ---------------------------------------------------------------------------------------------- PPO
-def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None):
+def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None, fused_loss: bool | None = None):
     """biped_tasks/utils/cleanrl/ppo.py:121-369 (the module docstring lists the deviations).  ``on_step(step_index,
-    obs, action, logprob, value)`` is a read-only observer of each stored transition (tests, probes)."""
+    obs, action, logprob, value)`` is a read-only observer of each stored transition (tests, probes).  ``fused_loss``
+    (None: ``H12_CLEANRL_HEAD_FUSED=1``) selects the fused loss head and, on CUDA, the captured update."""
     from .ppo import _Logger
+    from .ppo_head import cleanrl_fused_loss_enabled
+
+    fused_loss = cleanrl_fused_loss_enabled() if fused_loss is None else bool(fused_loss)
 
     if ppo_cfg.logger == "wandb":
         raise RuntimeError("logger='wandb' is not available on this stack (no wandb package); use 'tensorboard', "
@@ -399,7 +509,23 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None):
     agent = Agent(envs).to(device)
     if resume_path is not None:
         agent.load_state_dict(torch.load(resume_path, map_location=device, weights_only=True))
-    optimizer = optim.RAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5)
+    lr_t = updater = None
+    if fused_loss:
+        if device.type == "cuda":
+            from . import _learn
+
+            if int(np.prod(act_shape)) > _learn.ppo_head_max_actions():
+                raise ValueError(f"fused_loss: {int(np.prod(act_shape))} actions, the loss head takes at most "
+                                 f"{_learn.ppo_head_max_actions()}")
+            # the learning rate as a device scalar: the annealing rewrites it under a captured step
+            lr_t = torch.tensor(LEARNING_RATE, dtype=torch.float32, device=device)
+            optimizer = optim.RAdam(agent.parameters(), lr=lr_t, eps=1e-5, capturable=True)
+        else:
+            optimizer = optim.RAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5)
+        updater = _FusedUpdate(agent, optimizer, ppo_cfg, BATCH_SIZE, device, _graph_enabled(device))
+    else:
+        optimizer = optim.RAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5)
+    lr_host = LEARNING_RATE
     collector = _Collector(agent, _graph_enabled(device))
 
     obs = torch.zeros((NUM_STEPS, NUM_ENVS, *obs_shape), dtype=torch.float, device=device)
@@ -421,7 +547,11 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None):
         ep_infos = []
         if ANNEAL_LR:
             frac = 1.0 - (iteration - 1.0) / NUM_ITERATIONS
-            optimizer.param_groups[0]["lr"] = frac * LEARNING_RATE
+            if lr_t is not None:
+                lr_host = frac * LEARNING_RATE
+                lr_t.fill_(lr_host)
+            else:
+                optimizer.param_groups[0]["lr"] = frac * LEARNING_RATE
 
         # the first action of an iteration comes from the freshly updated weights; within the iteration the
         # normalisation of the new observation and the next action are one piece of work (one graph replay)
@@ -465,10 +595,15 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None):
 
         sums = torch.zeros(4, device=device)  # pg, entropy, v, surrogate
         clipfracs = []
+        if updater is not None:
+            updater.begin(b_obs, b_logprobs, b_actions, b_advantages, b_values, b_returns)
         for _epoch in range(UPDATES_EPOCHS):
             b_inds = torch.randperm(BATCH_SIZE, device=device)
             for start in range(0, BATCH_SIZE, MINIBATCH_SIZE):
                 mb_inds = b_inds[start:start + MINIBATCH_SIZE]
+                if updater is not None:
+                    updater.step(mb_inds)
+                    continue
                 _, newlogprob, entropy, newvalue = agent.get_action_and_value(b_obs[mb_inds], b_actions[mb_inds])
                 logratio = newlogprob - b_logprobs[mb_inds]
                 ratio = logratio.exp()
@@ -502,10 +637,14 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None):
                 optimizer.step()
 
         num_updates = UPDATES_EPOCHS * BATCH_SIZE / MINIBATCH_SIZE
-        pg, ent, vl, sur, cf = torch.cat([sums / num_updates, torch.stack(clipfracs).mean().reshape(1)]).tolist()
+        if updater is not None:
+            pg, ent, vl, sur, cf = updater.means(num_updates).tolist()
+        else:
+            pg, ent, vl, sur, cf = torch.cat([sums / num_updates, torch.stack(clipfracs).mean().reshape(1)]).tolist()
         t_end = time.time()
         scalars.update({"Loss/mean_pg_loss": pg, "Loss/mean_entropy_loss": ent, "Loss/mean_v_loss": vl,
-                        "Loss/mean_surrogate_loss": sur, "Loss/learning_rate": optimizer.param_groups[0]["lr"],
+                        "Loss/mean_surrogate_loss": sur,
+                        "Loss/learning_rate": lr_host if lr_t is not None else optimizer.param_groups[0]["lr"],
                         "Loss/clipfrac": cf, "Perf/collection_time": t_collect - t_start,
                         "Perf/learning_time": t_end - t_collect,
                         "Perf/total_fps": BATCH_SIZE / max(t_end - t_start, 1e-9)})

@@ -6,7 +6,11 @@ together with ``out`` = (surrogate loss, value loss, entropy mean, KL mean, tota
 one ``h12learn_ppo_head`` call (csrc/h12_ppo_head.hip: two launches), which gathers the rollout's per-sample tensors
 itself, applies the adaptive learning-rate rule and accumulates the statistics when asked to, and leaves the three
 gradients for the backward.  On CPU tensors the same node evaluates ``_minibatch``'s torch expressions and
-differentiates them with autograd, so it is bit-identical to the default path there."""
+differentiates them with autograd, so it is bit-identical to the default path there.
+
+``CleanRLHead`` is the same construction for the CleanRL trainer (h12env/cleanrl.py): the block of
+``cleanrl.PPO`` from ``logratio`` to ``loss`` over (mean, value, actor_logstd), ``out`` = (pg loss, entropy, v loss, total
+loss, clip fraction), one ``h12learn_cleanrl_head`` call on CUDA tensors and ``torch_cleanrl_head`` on CPU tensors."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -122,3 +126,98 @@ class PPOHead(torch.autograd.Function):
     def backward(ctx, g, _g_out):
         d_mean, d_value, d_param = ctx.saved_tensors
         return g * d_mean, g * d_value, g * d_param, None
+
+
+# ---------------------------------------------------------------------------------------------- CleanRL
+def cleanrl_fused_loss_enabled() -> bool:
+    """H12_CLEANRL_HEAD_FUSED=1: cleanrl.PPO computes the loss head with CleanRLHead."""
+    import os
+
+    return os.environ.get("H12_CLEANRL_HEAD_FUSED", "0") == "1"
+
+
+@dataclass
+class CleanRLInputs:
+    """What the CleanRL head reads besides the networks' outputs: the minibatch's rows ``idx`` of the flattened rollout
+    tensors (n_src rows each; returns_n and values_n are normalised by value_rms), the agent's ``value_rms`` module
+    (read, never updated) and the trainer's coefficients."""
+    idx: torch.Tensor
+    old_log_prob: torch.Tensor
+    advantages: torch.Tensor
+    returns_n: torch.Tensor
+    values_n: torch.Tensor
+    actions: torch.Tensor
+    value_rms: torch.nn.Module
+    clip_coef: float
+    ent_coef: float
+    vf_coef: float
+    norm_adv: bool
+    clip_vloss: bool
+    stats_accum: torch.Tensor | None = None  # CUDA only: ``out`` is added to its five elements
+
+
+def torch_cleanrl_head(mean, value, logstd, h: CleanRLInputs):
+    """``cleanrl.PPO``'s minibatch from the networks' outputs to the loss, operation for operation (the Normal of
+    ``Agent.get_action_and_value`` included): (loss, out)."""
+    mb_inds = h.idx
+    action_logstd = logstd.expand_as(mean)
+    action_std = torch.exp(action_logstd)
+    probs = Normal(mean, action_std, validate_args=None if not mean.is_cuda else False)
+    newlogprob, entropy = probs.log_prob(h.actions[mb_inds]).sum(1), probs.entropy().sum(1)
+    logratio = newlogprob - h.old_log_prob[mb_inds]
+    ratio = logratio.exp()
+    with torch.no_grad():
+        clipfrac = ((ratio - 1.0).abs() > h.clip_coef).float().mean()
+
+    mb_advantages = h.advantages[mb_inds]
+    if h.norm_adv:
+        mb_advantages = (mb_advantages - mb_advantages.mean()) / (mb_advantages.std() + 1e-8)
+
+    pg_loss1 = -mb_advantages * ratio
+    pg_loss2 = -mb_advantages * torch.clamp(ratio, 1 - h.clip_coef, 1 + h.clip_coef)
+    pg_loss = torch.max(pg_loss1, pg_loss2).mean()
+
+    newvalue = h.value_rms(value.view(-1), update=False)
+    if h.clip_vloss:
+        v_loss_unclipped = (newvalue - h.returns_n[mb_inds]) ** 2
+        v_clipped = h.values_n[mb_inds] + torch.clamp(newvalue - h.values_n[mb_inds], -h.clip_coef, h.clip_coef)
+        v_loss_clipped = (v_clipped - h.returns_n[mb_inds]) ** 2
+        v_loss = 0.5 * torch.max(v_loss_unclipped, v_loss_clipped).mean()
+    else:
+        v_loss = 0.5 * ((newvalue - h.returns_n[mb_inds]) ** 2).mean()
+
+    entropy_loss = entropy.mean()
+    loss = pg_loss - h.ent_coef * entropy_loss + v_loss * h.vf_coef
+    out = torch.stack([pg_loss.detach(), entropy_loss.detach(), v_loss.detach(), loss.detach(), clipfrac])
+    return loss, out
+
+
+class CleanRLHead(torch.autograd.Function):
+    """(loss, out) = CleanRLHead.apply(mean [m][A], value [m][1], actor_logstd [1][A], CleanRLInputs).  ``out`` carries
+    no gradient; the backward returns the three gradients the forward computed, scaled by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, mean, value, logstd, h: CleanRLInputs):
+        if mean.is_cuda:
+            rms = h.value_rms
+            d_mean, d_value, d_logstd, out = _learn.cleanrl_head(
+                mean, value, logstd, h.idx, h.old_log_prob, h.advantages, h.returns_n, h.values_n, h.actions,
+                rms.running_mean, rms.running_var, rms.epsilon, h.clip_coef, h.ent_coef, h.vf_coef, h.norm_adv,
+                h.clip_vloss, stats_accum=h.stats_accum)
+            loss = out[3].clone()
+            d_value, d_logstd = d_value.view_as(value), d_logstd.view_as(logstd)
+        else:
+            leaves = [t.detach().requires_grad_(True) for t in (mean, value, logstd)]
+            with torch.enable_grad():
+                loss, out = torch_cleanrl_head(*leaves, h)
+                d_mean, d_value, d_logstd = torch.autograd.grad(loss, leaves)
+            loss = loss.detach()
+        ctx.save_for_backward(d_mean, d_value, d_logstd)
+        ctx.mark_non_differentiable(out)
+        return loss, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_out):
+        d_mean, d_value, d_logstd = ctx.saved_tensors
+        return g * d_mean, g * d_value, g * d_logstd, None

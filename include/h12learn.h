@@ -261,6 +261,80 @@ int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream);
 
 const char* h12learn_last_error(void);
 
+/* ---- fused CleanRL loss head (csrc/h12_ppo_head.hip): the block of cleanrl.PPO (h12env/cleanrl.py) from `logratio` to
+ * `loss`, with the minibatch gathers, the per-minibatch advantage normalisation, the de-normalisation of the critic's
+ * output through value_rms (update=False) and the gradients of
+ *     loss = mean(pg) - ent_coef * entropy + vf_coef * 0.5 * mean(v)
+ * with respect to the actor's mean, the critic's value and actor_logstd, in three launches (two without norm_adv).
+ *
+ * Rows.  m rows of network outputs; row r reads the rollout's per-sample tensors at source row k = idx[r] (idx null:
+ * k = r, n_src >= m); an entry outside [0, n_src) is clamped into it.  Per row, in fp32 on separately rounded operations:
+ *     log_prob = sum_a  -(actions[k][a] - mean[r][a])^2 / (2 sigma^2) - logstd[a] - log(sqrt(2 pi)),  sigma = exp(logstd)
+ *     ratio    = exp(log_prob - old_log_prob[k])
+ *     clip row = |ratio - 1| > clip_coef                                   (strict)
+ *     adv      = advantages[k];  norm_adv: (adv - mean_mb) / (std_mb + 1e-8), mean_mb and std_mb (correction 1) over
+ *                the m gathered advantages
+ *     pg row   = max(-adv * ratio, -adv * clamp(ratio, 1 - clip_coef, 1 + clip_coef))
+ *     nv       = (value[r] - *value_mean) / sqrt(*value_var + value_eps)
+ *     v row    = clip_vloss ? max((nv - returns_n[k])^2,
+ *                                 (values_n[k] + clamp(nv - values_n[k], -clip_coef, clip_coef) - returns_n[k])^2)
+ *                           : (nv - returns_n[k])^2
+ *     entropy  = sum_a  0.5 + 0.5 log(2 pi) + logstd[a]                    (the same for every row: computed once)
+ * The bounds 1 -+ clip_coef, +-clip_coef, the two coefficients and value_eps are formed in double and narrowed once.
+ * Tie / boundary rule: that of h12learn_ppo_head above (closed-interval clamp, half weights on an exact max tie).
+ *
+ * Advantage statistics: each block of h12learn_cleanrl_head_rows() rows writes the shifted two-pass (count, mean, M2) of
+ * its rows' gathered advantages in fp64; every block of the row kernel merges these partials itself in block-index order
+ * (Chan's update, fp64) and narrows mean and sqrt(M2 / (m - 1)) once.  No E[x^2] - mean^2 anywhere.
+ *
+ * Outputs: d_mean [m][A], d_value [m] (through the de-normalisation: / sqrt(*value_var + value_eps)), d_logstd [A],
+ * out[5] = pg loss, entropy, v loss (the 0.5 included), total loss, clip fraction.  stats_accum not null:
+ * stats_accum[0..4] += out[0..4].
+ *
+ * Reductions as for h12learn_ppo_head: fp32 terms, fp64 row-order block partials, an in-order fold; no atomics, nothing
+ * to initialise, every output bitwise reproducible from run to run.  Inputs are assumed finite. */
+typedef struct h12learn_cleanrl_head_args {
+  long long m;     /* rows of mean / value */
+  long long n_src; /* rows of the rollout tensors */
+  int A;           /* actions, 1 .. h12learn_ppo_head_max_actions() */
+  int norm_adv;    /* needs m >= 2 (the std of one element is NaN) */
+  int clip_vloss;
+  int reserved;    /* 0 */
+  const float* mean;         /* [m][A] */
+  const float* value;        /* [m] */
+  const float* logstd;       /* [A] */
+  const long long* idx;      /* [m] or null */
+  const float* old_log_prob; /* [n_src] */
+  const float* advantages;   /* [n_src] */
+  const float* returns_n;    /* [n_src], normalised by value_rms */
+  const float* values_n;     /* [n_src], normalised by value_rms */
+  const float* actions;      /* [n_src][A] */
+  const float* value_mean;   /* device scalar: value_rms.running_mean */
+  const float* value_var;    /* device scalar: value_rms.running_var */
+  double value_eps;          /* value_rms.epsilon, >= 0 */
+  double clip_coef;          /* >= 0 */
+  double ent_coef;
+  double vf_coef;
+  float* d_mean;      /* [m][A] */
+  float* d_value;     /* [m] */
+  float* d_logstd;    /* [A] */
+  float* out;         /* [5] */
+  float* stats_accum; /* [5], or null */
+  void* workspace;    /* 8-byte aligned, h12learn_cleanrl_head_workspace_bytes(m, A) */
+  size_t workspace_bytes;
+} h12learn_cleanrl_head_args;
+
+/* Rows of a block (the row tile R of both the advantage kernel and the row kernel). */
+int h12learn_cleanrl_head_rows(void);
+
+/* Bytes of workspace for m rows of A actions: ceil(m / R) blocks of 3 (count, mean, M2) + 3 + A fp64 partials.  0 with
+ * h12learn_last_error set when m or A is invalid. */
+size_t h12learn_cleanrl_head_workspace_bytes(long long m, int A);
+
+/* Three launches (advantage partials, rows, fold; without norm_adv the first is left out).  No output may overlap an
+ * input. */
+int h12learn_cleanrl_head(const h12learn_cleanrl_head_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

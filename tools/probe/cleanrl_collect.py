@@ -3,6 +3,8 @@
 
     python tools/probe/cleanrl_collect.py [--num_envs 4096] [--steps 24] [--rounds 4] [--iters 5] [--out FILE]
     python tools/probe/cleanrl_collect.py --mode rocprof [--out FILE]
+    python tools/probe/cleanrl_collect.py --mode head [--rounds 4] [--iters 6] [--out FILE]
+    python tools/probe/cleanrl_collect.py --mode head_trace --arm default|fused_eager|fused_graphed [--out FILE]
 
 time (default): the two arms alternate in one process on one env (arm A fused, arm B torch, A, B, ...); each
 turn is one PPO() call of 1 + iters iterations whose first iteration (graph capture, allocator warm-up) is
@@ -11,6 +13,14 @@ statistics and the iteration ends on the transfer of the loss sums, so both are 
 collection ms / iteration and whole-iteration ms, median and min per arm.
 rocprof: starts `rocprofv3 --kernel-trace --stats -- python <this file> --mode short` as a child process (this
 process never opens the GPU) and reports calls / average / min / max of the new kernels from its stats CSV.
+head: the update's three arms alternate in one process on one env: ``default`` (the switch off), ``fused_eager``
+(fused_loss with H12_PPO_GRAPH=0, which also collects eagerly: compare its learning time, not its iteration) and
+``fused_graphed``.  Learning ms and whole-iteration ms per arm: median and minimum over all turns, and the median of
+every turn on its own, which is the spread between repeats of one arm.  Every logged loss and every parameter of every
+arm is asserted finite.
+head_trace: one arm under `rocprofv3 --kernel-trace --stats` in a child process; the update's dispatches (from an
+iteration's GAE kernel to the next env step) per minibatch, split into GEMMs, ELU, optimiser and gradient clip (the
+multi-tensor kernels), the head's kernels and the rest.
 """
 from __future__ import annotations
 
@@ -87,6 +97,125 @@ def mode_time(a):
     return out
 
 
+HEAD_ARMS = {"default": (False, "1"), "fused_eager": (True, "0"), "fused_graphed": (True, "1")}
+
+
+def run_head_arm(env, arm: str, steps: int, iters: int, tmp: str):
+    import math
+
+    import torch
+    from biped_tasks.tasks.agents import H12_12dof_FlatCleanRlPPOCfg
+    from h12env import cleanrl
+
+    fused_loss, graph = HEAD_ARMS[arm]
+    os.environ["H12_CLEANRL_FUSED"] = "1"
+    os.environ["H12_PPO_GRAPH"] = graph
+    cfg = H12_12dof_FlatCleanRlPPOCfg(num_steps=steps, num_iterations=1 + iters, save_interval=10 ** 9)
+    cfg.minibatch_size = min(cfg.minibatch_size, steps * env.unwrapped.num_envs)
+    run = tempfile.mkdtemp(dir=tmp)
+    torch.manual_seed(1)
+    agent = cleanrl.PPO(env, cfg, run, fused_loss=fused_loss)
+    torch.cuda.synchronize()
+    all_lines = [json.loads(x) for x in open(os.path.join(run, "metrics.jsonl"))]
+    for x in all_lines:
+        bad = {k: v for k, v in x.items() if k.startswith("Loss/") and not math.isfinite(v)}
+        assert not bad, (arm, x["iter"], bad)
+    for k, v in agent.state_dict().items():
+        assert bool(torch.isfinite(v).all()), (arm, k)
+    lines = all_lines[1:]
+    return ([1e3 * x["Perf/learning_time"] for x in lines],
+            [1e3 * (x["Perf/collection_time"] + x["Perf/learning_time"]) for x in lines],
+            {"minibatch_size": cfg.minibatch_size, "updates_epochs": cfg.updates_epochs})
+
+
+def mode_head(a):
+    env = make_env(a.num_envs)
+    res = {arm: ([], [], []) for arm in HEAD_ARMS}
+    with tempfile.TemporaryDirectory() as tmp:
+        for _ in range(a.rounds):
+            for arm in HEAD_ARMS:
+                learn, whole, shape = run_head_arm(env, arm, a.steps, a.iters, tmp)
+                res[arm][0].extend(learn)
+                res[arm][1].extend(whole)
+                res[arm][2].append(statistics.median(learn))
+    env.close()
+    out = {"task": TASK, "num_envs": a.num_envs, "steps": a.steps, "iterations_per_arm": a.rounds * a.iters,
+           "finite": "every logged loss and every parameter, every arm", **shape}
+    for arm, (learn, whole, turns) in res.items():
+        out[arm] = {"learning_ms_median": statistics.median(learn), "learning_ms_min": min(learn),
+                    "iteration_ms_median": statistics.median(whole), "iteration_ms_min": min(whole),
+                    "learning_ms_median_per_turn": turns}
+    return out
+
+
+def mode_head_short(a):
+    env = make_env(a.num_envs)
+    with tempfile.TemporaryDirectory() as tmp:
+        _, _, shape = run_head_arm(env, a.arm, a.steps, 2, tmp)
+    env.close()
+    return {"ok": True, **shape}
+
+
+def _category(name: str) -> str:
+    low = name.lower()
+    if "cleanrl_" in low:
+        return "head"
+    if "cijk" in low or "gemm" in low:
+        return "gemm"
+    if "elu" in low:
+        return "elu"
+    if "multi_tensor" in low:
+        return "optimiser_and_clip"
+    return "rest"
+
+
+def mode_head_trace(a):
+    iters = 3  # of head_short: 1 + 2
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", tmp, "-o", "run", "--", sys.executable,
+               str(Path(__file__).resolve()), "--mode", "head_short", "--arm", a.arm, "--num_envs", str(a.num_envs),
+               "--steps", str(a.steps)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
+        if r.returncode != 0:
+            raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
+        shape = json.loads(r.stdout[r.stdout.rindex('{\n "ok"'):])
+        files = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)
+        if not files:
+            raise RuntimeError("rocprofv3 wrote no kernel_trace.csv")
+        rows = sorted(csv.DictReader(open(files[0])), key=lambda x: int(x["Start_Timestamp"]))
+    # an iteration's update: after its GAE kernel, until the env steps again (the last update runs to the end)
+    cats, names, in_update, updates = {}, {}, False, 0
+    for row in rows:
+        name = row["Kernel_Name"]
+        if "gae_soft_kernel" in name:
+            in_update, updates = True, updates + 1
+            continue
+        if "step_kernel" in name:
+            in_update = False
+        if not in_update:
+            continue
+        ns = int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
+        c = cats.setdefault(_category(name), [0, 0])
+        c[0] += 1
+        c[1] += ns
+        n = names.setdefault(name[:96], [0, 0])
+        n[0] += 1
+        n[1] += ns
+    assert updates == iters, updates
+    n_mb = updates * shape["updates_epochs"] * -(-a.num_envs * a.steps // shape["minibatch_size"])
+    total = sum(c[1] for c in cats.values())
+    out = {"command": f"rocprofv3 --kernel-trace --stats -- python tools/probe/cleanrl_collect.py --mode head_short "
+                      f"--arm {a.arm}", "arm": a.arm, "num_envs": a.num_envs, "steps": a.steps, **shape,
+           "minibatches_traced": n_mb, "launches_per_minibatch": sum(c[0] for c in cats.values()) / n_mb,
+           "gpu_us_per_minibatch": total / n_mb / 1e3, "split": {}}
+    for k, (calls, ns) in sorted(cats.items()):
+        out["split"][k] = {"launches_per_minibatch": calls / n_mb, "gpu_us_per_minibatch": ns / n_mb / 1e3,
+                           "share": ns / total}
+    top = sorted(names.items(), key=lambda kv: -kv[1][1])[:25]
+    out["kernels"] = {k: {"calls_per_minibatch": c / n_mb, "avg_us": ns / c / 1e3} for k, (c, ns) in top}
+    return out
+
+
 def mode_short(a):
     env = make_env(a.num_envs)
     with tempfile.TemporaryDirectory() as tmp:
@@ -118,14 +247,16 @@ def mode_rocprof(a):
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("time", "short", "rocprof"), default="time")
+    ap.add_argument("--mode", choices=("time", "short", "rocprof", "head", "head_short", "head_trace"), default="time")
+    ap.add_argument("--arm", choices=tuple(HEAD_ARMS), default="default")
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
-    out = {"time": mode_time, "short": mode_short, "rocprof": mode_rocprof}[a.mode](a)
+    out = {"time": mode_time, "short": mode_short, "rocprof": mode_rocprof, "head": mode_head,
+           "head_short": mode_head_short, "head_trace": mode_head_trace}[a.mode](a)
     s = json.dumps(out, indent=1)
     print(s)
     if a.out:

@@ -19,7 +19,10 @@
 // No atomics, no counters, nothing to initialise: every output is a fixed-order sum.  The summed terms are fp32, the
 // accumulators and the partials fp64, so a sum carries the rounding of its terms only.
 //
-// The CleanRL trainer's head (h12learn_cleanrl_head) follows the PPO head's kernels below, on the same helpers.
+// The CleanRL trainer's head (h12learn_cleanrl_head) follows the PPO head's kernels below.  What the two heads compute
+// alike (the rows' bookkeeping, the clipped surrogate, the clipped value error, the two kinds of sum, the block's
+// partial) is one device function each; their loads, value transform, third scalar and gradient scales differ and stay
+// in two rows kernels and two fold epilogues.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -29,24 +32,36 @@
 // the error record of h12_learn.hip (not part of the ABI)
 int h12_learn_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3), visibility("hidden")));
 
+// No multiply is fused into a following add anywhere in this file: the kernels restate torch's separately rounded
+// operations.  At file scope, so that a helper inlined into a kernel cannot carry another setting than the kernel.
+#pragma clang fp contract(off)
+
 namespace {
 
 constexpr int HEAD_WAVES = 4;
 constexpr int HEAD_ROWS = 64;        // rows per block R
 constexpr int HEAD_UNROLL = 4;       // passes whose loads are in flight together
 constexpr int HEAD_MAX_A = 32;
-constexpr int HEAD_SC = 3;           // per-row scalars that are summed: surrogate, value, KL
+constexpr int HEAD_SC = 3;           // per-row scalars that are summed: surrogate, value, KL (CleanRL: clip indicator)
 constexpr int FOLD_THREADS = 256;
 constexpr int FOLD_CHUNK = 128;      // blocks staged in LDS at a time
 constexpr int FOLD_PER_THREAD = (FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A) + FOLD_THREADS - 1) / FOLD_THREADS;
 constexpr int SUM_BATCH = 8;        // LDS reads in flight ahead of a serial sum
+template <int G>                    // G lanes per row: a block's passes, of HEAD_WAVES * (64 / G) rows each
+constexpr int PASSES = HEAD_ROWS / (HEAD_WAVES * (64 / G));
+static_assert(PASSES<16> % HEAD_UNROLL == 0 && PASSES<32> % HEAD_UNROLL == 0,
+              "the passes are taken HEAD_UNROLL at a time");
+static_assert(HEAD_ROWS % SUM_BATCH == 0, "the row sums read SUM_BATCH rows at a time");
 constexpr double LOG_SQRT_2PI_D = 0.918938533204672741780329736406;  // log(sqrt(2 pi)), also 0.5 log(2 pi)
 constexpr float LOG_SQRT_2PI = (float)LOG_SQRT_2PI_D;
 
-struct HeadScalars {
-  float lo, hi;      // 1 -+ clip_param
+struct LossScalars {  // the coefficients both heads have, narrowed once on the host
+  float lo, hi;      // 1 -+ the clip coefficient
   float clip;        // the value clip
   float vcoef, ecoef;
+};
+
+struct HeadScalars : LossScalars {
   float kl_up, kl_down;  // 2 desired_kl, desired_kl / 2
 };
 
@@ -72,10 +87,48 @@ __device__ __forceinline__ void max_weights(float x, float y, float& wx, float& 
   wy = x < y ? 1.0f : (x == y ? 0.5f : 0.0f);
 }
 
-// The two sums below are the loops of ppo_head_rows_kernel and ppo_head_fold_kernel as functions, for the CleanRL head's
-// kernels.  Those two kernels keep their loops inline: routed through these functions they compile to other code
-// (block order and branches), and their code object is to stay what it was.
-//
+// ---- the rows both heads' rows kernels walk: a block's HEAD_ROWS rows in passes of HEAD_WAVES * (64 / G) rows
+// the block row of lane group `grp` of wave `w` in pass `pass`
+template <int G>
+__device__ __forceinline__ int pass_row(int pass, int w, int grp) {
+  return pass * (HEAD_WAVES * (64 / G)) + w * (64 / G) + grp;
+}
+
+// the row that is read for row r of m: rows past m re-read row m - 1 and store nothing
+__device__ __forceinline__ long long read_row(long long r, long long m) { return r < m ? r : m - 1; }
+
+// entry j of idx (null: j itself), and its clamp into the n_src source rows.  Two functions: the rows kernels issue
+// every index load of a batch before the first clamp waits for one.
+__device__ __forceinline__ long long source_row(const long long* idx, long long j) { return idx ? idx[j] : j; }
+__device__ __forceinline__ long long clamp_row(long long k, long long n_src) {
+  return k < 0 ? 0 : (k < n_src ? k : n_src - 1);
+}
+
+// the clipped surrogate of one row, max(-adv ratio, -adv clamp(ratio, lo, hi)); g_lp = d (that / m) / d log_prob
+__device__ __forceinline__ float surrogate_row(float adv, float ratio, float lo, float hi, float inv_m, float& g_lp) {
+  const float s1 = -adv * ratio;
+  const float s2 = -adv * fminf(fmaxf(ratio, lo), hi);
+  const bool inside = ratio >= lo && ratio <= hi;
+  float w1, w2;
+  max_weights(s1, s2, w1, w2);
+  g_lp = inv_m * (-adv * (w1 + (inside ? w2 : 0.0f))) * ratio;
+  return fmaxf(s1, s2);
+}
+
+// the clipped value error of one row, max((v - ret)^2, (target + clamp(v - target, -clip, clip) - ret)^2); dv = its
+// derivative with respect to v
+__device__ __forceinline__ float clipped_value_row(float v, float target, float ret, float clip, float& dv) {
+  const float dvt = v - target;
+  const float vc = target + fminf(fmaxf(dvt, -clip), clip);
+  const bool inside_v = dvt >= -clip && dvt <= clip;
+  const float e1 = v - ret, e2 = vc - ret;
+  const float q1 = e1 * e1, q2 = e2 * e2;
+  float v1, v2;
+  max_weights(q1, q2, v1, v2);
+  dv = v1 * (2.0f * e1) + (inside_v ? v2 * (2.0f * e2) : 0.0f);
+  return fmaxf(q1, q2);
+}
+
 // row-order sum of one column of an LDS array of HEAD_ROWS rows, `stride` floats apart (fp64 accumulator: the sum then
 // carries the rounding of its fp32 terms only); SUM_BATCH reads in flight ahead of the dependent adds
 __device__ __forceinline__ double rows_sum(const float* col, int stride) {
@@ -88,6 +141,20 @@ __device__ __forceinline__ double rows_sum(const float* col, int stride) {
     for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
   }
   return acc;
+}
+
+// a block's partial, after the barrier behind its rows: threads [0, A) of wave 0 take the parameter columns of s_dp,
+// threads [64, 64 + HEAD_SC) the scalars of s_sc
+template <int G>
+__device__ __forceinline__ void write_partial(const float (*s_dp)[G], const float (*s_sc)[HEAD_SC + 1], int A, int tid,
+                                              double* partial) {
+  double* out = partial + (size_t)blockIdx.x * (size_t)(HEAD_SC + A);
+  if (tid < A) {
+    out[HEAD_SC + tid] = rows_sum(&s_dp[0][tid], G);
+  } else if (tid >= 64 && tid < 64 + HEAD_SC) {
+    const int q = tid - 64;
+    out[q] = rows_sum(&s_sc[0][q], HEAD_SC + 1);
+  }
 }
 
 // the fold's sums: `blocks` partials of P quantities each are staged through s_buf (FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)
@@ -128,12 +195,6 @@ __device__ __forceinline__ double fold_sum(const double* partial, int blocks, in
 template <int G>
 __global__ __launch_bounds__(HEAD_WAVES * 64) void ppo_head_rows_kernel(h12learn_ppo_head_args p, HeadScalars sc,
                                                                         double* partial) {
-#pragma clang fp contract(off)
-  constexpr int GROUPS = 64 / G;                    // rows of a wave per pass
-  constexpr int PASS_ROWS = HEAD_WAVES * GROUPS;    // rows of the block per pass
-  constexpr int PASSES = HEAD_ROWS / PASS_ROWS;
-  static_assert(PASSES % HEAD_UNROLL == 0, "the passes are taken HEAD_UNROLL at a time");
-  static_assert(HEAD_ROWS % SUM_BATCH == 0, "the row sums read SUM_BATCH rows at a time");
   __shared__ float s_dp[HEAD_ROWS][G];
   __shared__ float s_sc[HEAD_ROWS][HEAD_SC + 1];
 
@@ -155,22 +216,20 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void ppo_head_rows_kernel(h12learn
   const float inv_var = inv_sigma * inv_sigma;
 
   const long long block_row = (long long)blockIdx.x * HEAD_ROWS;
-  for (int p0 = 0; p0 < PASSES; p0 += HEAD_UNROLL) {
+  for (int p0 = 0; p0 < PASSES<G>; p0 += HEAD_UNROLL) {
     long long rr[HEAD_UNROLL], k[HEAD_UNROLL];
     int rl[HEAD_UNROLL];
 #pragma unroll
     for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 1: the indices
-      rl[i] = (p0 + i) * PASS_ROWS + w * GROUPS + grp;
-      const long long r = block_row + rl[i];
-      rr[i] = r < m ? r : m - 1;  // rows past m re-read row m - 1 and store nothing
-      const long long rb = rr[i] >= B ? rr[i] - B : rr[i];
-      k[i] = p.idx ? p.idx[rb] : rb;
+      rl[i] = pass_row<G>(p0 + i, w, grp);
+      rr[i] = read_row(block_row + rl[i], m);
+      k[i] = source_row(p.idx, rr[i] >= B ? rr[i] - B : rr[i]);  // a mirrored row has its original's sources
     }
     float mu[HEAD_UNROLL], act[HEAD_UNROLL], omu[HEAD_UNROLL], osg[HEAD_UNROLL];
     float olp[HEAD_UNROLL], adv[HEAD_UNROLL], ret[HEAD_UNROLL], tv[HEAD_UNROLL], val[HEAD_UNROLL];
 #pragma unroll
     for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 2: everything else
-      k[i] = k[i] < 0 ? 0 : (k[i] < p.n_src ? k[i] : p.n_src - 1);
+      k[i] = clamp_row(k[i], p.n_src);
       const size_t er = (size_t)rr[i] * (size_t)A + ac, ek = (size_t)k[i] * (size_t)A + ac;
       mu[i] = p.mean[er];
       act[i] = p.actions[p.actions_direct ? er : ek];
@@ -201,30 +260,17 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void ppo_head_rows_kernel(h12learn
       float g_lp = 0.0f;
       if (a == 0) {
         const float ratio = expf(log_prob - olp[i]);
-        const float s1 = -adv[i] * ratio;
-        const float s2 = -adv[i] * fminf(fmaxf(ratio, sc.lo), sc.hi);
-        const bool inside = ratio >= sc.lo && ratio <= sc.hi;
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        g_lp = inv_m * (-adv[i] * (w1 + (inside ? w2 : 0.0f))) * ratio;
+        const float surr = surrogate_row(adv[i], ratio, sc.lo, sc.hi, inv_m, g_lp);
         float vl, dv;
         if (p.use_clipped_value_loss) {
-          const float dvt = val[i] - tv[i];
-          const float vc = tv[i] + fminf(fmaxf(dvt, -sc.clip), sc.clip);
-          const bool inside_v = dvt >= -sc.clip && dvt <= sc.clip;
-          const float e1 = val[i] - ret[i], e2 = vc - ret[i];
-          const float q1 = e1 * e1, q2 = e2 * e2;
-          float v1, v2;
-          max_weights(q1, q2, v1, v2);
-          vl = fmaxf(q1, q2);
-          dv = v1 * (2.0f * e1) + (inside_v ? v2 * (2.0f * e2) : 0.0f);
+          vl = clipped_value_row(val[i], tv[i], ret[i], sc.clip, dv);
         } else {
           const float e = ret[i] - val[i];
           vl = e * e;
           dv = -2.0f * e;
         }
         if (live) p.d_value[rr[i]] = (sc.vcoef * inv_m) * dv;
-        s_sc[rl[i]][0] = live ? fmaxf(s1, s2) : 0.0f;
+        s_sc[rl[i]][0] = live ? surr : 0.0f;
         s_sc[rl[i]][1] = live ? vl : 0.0f;
         s_sc[rl[i]][2] = live && rr[i] < B ? kl : 0.0f;
       }
@@ -235,36 +281,11 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void ppo_head_rows_kernel(h12learn
     }
   }
   __syncthreads();
-  // row-order sums: threads [0, A) of wave 0 take d_param's columns, threads [64, 64 + HEAD_SC) the scalars
-  // (fp64 accumulators: the sums then carry the rounding of their fp32 terms only)
-  double* out = partial + (size_t)blockIdx.x * (size_t)(HEAD_SC + A);
-  if (tid < A) {
-    double acc = 0.0;
-    for (int r = 0; r < HEAD_ROWS; r += SUM_BATCH) {  // SUM_BATCH reads in flight ahead of the dependent adds
-      float v[SUM_BATCH];
-#pragma unroll
-      for (int j = 0; j < SUM_BATCH; ++j) v[j] = s_dp[r + j][tid];
-#pragma unroll
-      for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
-    }
-    out[HEAD_SC + tid] = acc;
-  } else if (tid >= 64 && tid < 64 + HEAD_SC) {
-    const int q = tid - 64;
-    double acc = 0.0;
-    for (int r = 0; r < HEAD_ROWS; r += SUM_BATCH) {
-      float v[SUM_BATCH];
-#pragma unroll
-      for (int j = 0; j < SUM_BATCH; ++j) v[j] = s_sc[r + j][q];
-#pragma unroll
-      for (int j = 0; j < SUM_BATCH; ++j) acc += (double)v[j];
-    }
-    out[q] = acc;
-  }
+  write_partial<G>(s_dp, s_sc, A, tid, partial);
 }
 
 __global__ __launch_bounds__(FOLD_THREADS) void ppo_head_fold_kernel(h12learn_ppo_head_args p, HeadScalars sc,
                                                                       const double* partial, int blocks) {
-#pragma clang fp contract(off)
   __shared__ double s_buf[FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)];
   __shared__ double s_fin[HEAD_SC + HEAD_MAX_A];
   __shared__ double s_ent[HEAD_MAX_A];
@@ -276,35 +297,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void ppo_head_fold_kernel(h12learn_pp
   const float lr = tid == 0 && p.lr ? *p.lr : 0.0f;
   float st[3] = {0.0f, 0.0f, 0.0f};
   if (tid == 0 && p.stats_accum) st[0] = p.stats_accum[0], st[1] = p.stats_accum[1], st[2] = p.stats_accum[2];
-  double acc = 0.0;
-  for (int c0 = 0; c0 < blocks; c0 += FOLD_CHUNK) {
-    const int cnt = blocks - c0 < FOLD_CHUNK ? blocks - c0 : FOLD_CHUNK;
-    const int total = cnt * P;
-    const double* src = partial + (size_t)c0 * (size_t)P;
-    double stage[FOLD_PER_THREAD];  // every load of the chunk issued before the first LDS store
-#pragma unroll
-    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
-      const int i = tid + j * FOLD_THREADS;
-      stage[j] = i < total ? src[i] : 0.0;
-    }
-#pragma unroll
-    for (int j = 0; j < FOLD_PER_THREAD; ++j) {
-      const int i = tid + j * FOLD_THREADS;
-      if (i < total) s_buf[i] = stage[j];
-    }
-    __syncthreads();
-    if (tid < P) {
-      // block-index order; SUM_BATCH reads in flight ahead of the dependent adds (a tail adds +0.0: no change)
-      for (int b = 0; b < cnt; b += SUM_BATCH) {
-        double v[SUM_BATCH];
-#pragma unroll
-        for (int j = 0; j < SUM_BATCH; ++j) v[j] = b + j < cnt ? s_buf[(b + j) * P + tid] : 0.0;
-#pragma unroll
-        for (int j = 0; j < SUM_BATCH; ++j) acc += v[j];
-      }
-    }
-    __syncthreads();  // the buffer is reused by the next chunk
-  }
+  const double acc = fold_sum(partial, blocks, P, tid, s_buf);
   if (tid < P) s_fin[tid] = acc;
   if (tid >= HEAD_SC && tid < P) {
     // d loss / d sigma = sum_r (...) - entropy_coef / sigma; the log parameter's gradient is that times sigma
@@ -350,29 +343,21 @@ __global__ __launch_bounds__(FOLD_THREADS) void ppo_head_fold_kernel(h12learn_pp
 //      order: thread j stages partial j and its two merge coefficients (the counts in front of block j are j HEAD_ROWS, so
 //      the divisions are off the dependent chain), thread 0 runs Chan's update over them.  Then the rows, as above.
 //   3. cleanrl_head_fold_kernel  the in-order fold, the entropy, the total, the statistics, d_logstd.
-constexpr int CLEAN_SC = 3;    // per-row scalars that are summed: pg, v, clip indicator
 constexpr int CLEAN_ADV = 3;   // a block's advantage partial: count, mean, M2
 constexpr int MERGE_CHUNK = HEAD_WAVES * 64;  // advantage partials staged in LDS at a time
-static_assert(CLEAN_SC <= HEAD_SC, "fold_sum's staging buffer is sized for HEAD_SC + HEAD_MAX_A quantities");
 
-struct CleanScalars {
-  float lo, hi;  // 1 -+ clip_coef
-  float clip;
-  float vcoef, ecoef;
+struct CleanScalars : LossScalars {
   float veps;
 };
 
 __global__ __launch_bounds__(64) void cleanrl_adv_kernel(h12learn_cleanrl_head_args p, double* apart) {
-#pragma clang fp contract(off)
   static_assert(HEAD_ROWS == 64, "one wave per block, a row per lane");
   const int lane = threadIdx.x;
   const long long first = (long long)blockIdx.x * HEAD_ROWS;
   const long long left = p.m - first;
   const int n = left < HEAD_ROWS ? (int)left : HEAD_ROWS;
   const bool live = lane < n;
-  const long long rr = live ? first + lane : p.m - 1;
-  long long k = p.idx ? p.idx[rr] : rr;
-  k = k < 0 ? 0 : (k < p.n_src ? k : p.n_src - 1);
+  const long long k = clamp_row(source_row(p.idx, read_row(first + lane, p.m)), p.n_src);
   const double x = (double)p.advantages[k];
   const double mean = group_sum<64, double>(live ? x : 0.0) / (double)n;
   const double d = live ? x - mean : 0.0;
@@ -391,7 +376,6 @@ __global__ __launch_bounds__(64) void cleanrl_adv_kernel(h12learn_cleanrl_head_a
 // dependent chain), thread 0 runs the chain.  Ends on a barrier.
 __device__ __forceinline__ void merge_adv(const double* apart, int blocks, long long m, int tid,
                                           double (*s_mg)[4], float* s_adv) {
-#pragma clang fp contract(off)
   double mean = 0.0, m2 = 0.0;  // thread 0's running merge
   for (int c0 = 0; c0 < blocks; c0 += MERGE_CHUNK) {
     const int cnt = blocks - c0 < MERGE_CHUNK ? blocks - c0 : MERGE_CHUNK;
@@ -426,14 +410,8 @@ template <int G>
 __global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12learn_cleanrl_head_args p,
                                                                             CleanScalars sc, const double* apart,
                                                                             double* partial, int blocks) {
-#pragma clang fp contract(off)
-  constexpr int GROUPS = 64 / G;
-  constexpr int PASS_ROWS = HEAD_WAVES * GROUPS;
-  constexpr int PASSES = HEAD_ROWS / PASS_ROWS;
-  static_assert(PASSES % HEAD_UNROLL == 0, "the passes are taken HEAD_UNROLL at a time");
-  static_assert(HEAD_ROWS % SUM_BATCH == 0, "the row sums read SUM_BATCH rows at a time");
   __shared__ float s_dp[HEAD_ROWS][G];
-  __shared__ float s_sc[HEAD_ROWS][CLEAN_SC + 1];
+  __shared__ float s_sc[HEAD_ROWS][HEAD_SC + 1];
   __shared__ double s_mg[MERGE_CHUNK][4];
   __shared__ float s_adv[2];
 
@@ -463,21 +441,20 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12l
   }
 
   const long long block_row = (long long)blockIdx.x * HEAD_ROWS;
-  for (int p0 = 0; p0 < PASSES; p0 += HEAD_UNROLL) {
+  for (int p0 = 0; p0 < PASSES<G>; p0 += HEAD_UNROLL) {
     long long rr[HEAD_UNROLL], k[HEAD_UNROLL];
     int rl[HEAD_UNROLL];
 #pragma unroll
     for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 1: the indices
-      rl[i] = (p0 + i) * PASS_ROWS + w * GROUPS + grp;
-      const long long r = block_row + rl[i];
-      rr[i] = r < m ? r : m - 1;  // rows past m re-read row m - 1 and store nothing
-      k[i] = p.idx ? p.idx[rr[i]] : rr[i];
+      rl[i] = pass_row<G>(p0 + i, w, grp);
+      rr[i] = read_row(block_row + rl[i], m);
+      k[i] = source_row(p.idx, rr[i]);
     }
     float mu[HEAD_UNROLL], act[HEAD_UNROLL];
     float olp[HEAD_UNROLL], adv[HEAD_UNROLL], ret[HEAD_UNROLL], vn[HEAD_UNROLL], val[HEAD_UNROLL];
 #pragma unroll
     for (int i = 0; i < HEAD_UNROLL; ++i) {  // batch 2: everything else
-      k[i] = k[i] < 0 ? 0 : (k[i] < p.n_src ? k[i] : p.n_src - 1);
+      k[i] = clamp_row(k[i], p.n_src);
       mu[i] = p.mean[(size_t)rr[i] * (size_t)A + ac];
       act[i] = p.actions[(size_t)k[i] * (size_t)A + ac];
       olp[i] = adv[i] = ret[i] = vn[i] = val[i] = 0.0f;
@@ -500,24 +477,11 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12l
       if (a == 0) {
         const float ad = p.norm_adv ? (adv[i] - adv_mean) / adv_den : adv[i];
         const float ratio = expf(log_prob - olp[i]);
-        const float s1 = -ad * ratio;
-        const float s2 = -ad * fminf(fmaxf(ratio, sc.lo), sc.hi);
-        const bool inside = ratio >= sc.lo && ratio <= sc.hi;
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        g_lp = inv_m * (-ad * (w1 + (inside ? w2 : 0.0f))) * ratio;
+        const float pg = surrogate_row(ad, ratio, sc.lo, sc.hi, inv_m, g_lp);
         const float nv = (val[i] - vmean) / vsd;
         float vl, dv;
         if (p.clip_vloss) {
-          const float dvt = nv - vn[i];
-          const float vc = vn[i] + fminf(fmaxf(dvt, -sc.clip), sc.clip);
-          const bool inside_v = dvt >= -sc.clip && dvt <= sc.clip;
-          const float e1 = nv - ret[i], e2 = vc - ret[i];
-          const float q1 = e1 * e1, q2 = e2 * e2;
-          float v1, v2;
-          max_weights(q1, q2, v1, v2);
-          vl = fmaxf(q1, q2);
-          dv = v1 * (2.0f * e1) + (inside_v ? v2 * (2.0f * e2) : 0.0f);
+          vl = clipped_value_row(nv, vn[i], ret[i], sc.clip, dv);
         } else {
           const float e = nv - ret[i];
           vl = e * e;
@@ -525,7 +489,7 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12l
         }
         // d loss / d v row = vf_coef * 0.5 / m; d nv / d value = 1 / sqrt(var + eps)
         if (live) p.d_value[rr[i]] = ((sc.vcoef * 0.5f * inv_m) * dv) / vsd;
-        s_sc[rl[i]][0] = live ? fmaxf(s1, s2) : 0.0f;
+        s_sc[rl[i]][0] = live ? pg : 0.0f;
         s_sc[rl[i]][1] = live ? vl : 0.0f;
         s_sc[rl[i]][2] = live && fabsf(ratio - 1.0f) > sc.clip ? 1.0f : 0.0f;
       }
@@ -536,26 +500,18 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void cleanrl_head_rows_kernel(h12l
     }
   }
   __syncthreads();
-  // row-order sums: threads [0, A) of wave 0 take d_logstd's columns, threads [64, 64 + CLEAN_SC) the scalars
-  double* out = partial + (size_t)blockIdx.x * (size_t)(CLEAN_SC + A);
-  if (tid < A) {
-    out[CLEAN_SC + tid] = rows_sum(&s_dp[0][tid], G);
-  } else if (tid >= 64 && tid < 64 + CLEAN_SC) {
-    const int q = tid - 64;
-    out[q] = rows_sum(&s_sc[0][q], CLEAN_SC + 1);
-  }
+  write_partial<G>(s_dp, s_sc, A, tid, partial);
 }
 
 __global__ __launch_bounds__(FOLD_THREADS) void cleanrl_head_fold_kernel(h12learn_cleanrl_head_args p, CleanScalars sc,
                                                                           const double* partial, int blocks) {
-#pragma clang fp contract(off)
   __shared__ double s_buf[FOLD_CHUNK * (HEAD_SC + HEAD_MAX_A)];
-  __shared__ double s_fin[CLEAN_SC + HEAD_MAX_A];
+  __shared__ double s_fin[HEAD_SC + HEAD_MAX_A];
   __shared__ double s_ent[HEAD_MAX_A];
   const int tid = threadIdx.x;
-  const int P = CLEAN_SC + p.A;
+  const int P = HEAD_SC + p.A;
   // issued before the partials are touched, so these latencies overlap the sums
-  const float logstd = tid >= CLEAN_SC && tid < P ? p.logstd[tid - CLEAN_SC] : 0.0f;
+  const float logstd = tid >= HEAD_SC && tid < P ? p.logstd[tid - HEAD_SC] : 0.0f;
   float st[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (tid == 0 && p.stats_accum) {
 #pragma unroll
@@ -563,10 +519,10 @@ __global__ __launch_bounds__(FOLD_THREADS) void cleanrl_head_fold_kernel(h12lear
   }
   const double acc = fold_sum(partial, blocks, P, tid, s_buf);
   if (tid < P) s_fin[tid] = acc;
-  if (tid >= CLEAN_SC && tid < P) {
+  if (tid >= HEAD_SC && tid < P) {
     // the entropy is sum_a logstd[a] + const, the same for every row: d (-ent_coef * entropy) / d logstd[a] = -ent_coef
-    p.d_logstd[tid - CLEAN_SC] = (float)(acc - (double)sc.ecoef);
-    s_ent[tid - CLEAN_SC] = (0.5 + LOG_SQRT_2PI_D) + (double)logstd;
+    p.d_logstd[tid - HEAD_SC] = (float)(acc - (double)sc.ecoef);
+    s_ent[tid - HEAD_SC] = (0.5 + LOG_SQRT_2PI_D) + (double)logstd;
   }
   __syncthreads();
   if (tid == 0) {
@@ -588,7 +544,60 @@ __global__ __launch_bounds__(FOLD_THREADS) void cleanrl_head_fold_kernel(h12lear
   }
 }
 
+// ---- the host side: what the two entry points check and do alike.  `head` is the name their messages begin with.
 long long head_blocks(long long m) { return (m + HEAD_ROWS - 1) / HEAD_ROWS; }
+
+// the workspace of a head whose blocks keep `extra` doubles besides their HEAD_SC + A sums; 0, with the error recorded,
+// for an m or an A out of range
+size_t workspace_bytes(const char* head, long long m, int A, int extra) {
+  if (m < 1) {
+    h12_learn_fail(H12LEARN_E_ARG, "%s_workspace_bytes: m = %lld (must be >= 1)", head, m);
+    return 0;
+  }
+  if (A < 1 || A > HEAD_MAX_A) {
+    h12_learn_fail(H12LEARN_E_ARG, "%s_workspace_bytes: A = %d (1 .. %d)", head, A, HEAD_MAX_A);
+    return 0;
+  }
+  return (size_t)head_blocks(m) * (size_t)(extra + HEAD_SC + A) * sizeof(double);
+}
+
+struct Required {
+  const void* ptr;
+  const char* name;
+};
+
+// The checks of the fields both argument structs have: m, A, n_src, the `rows` (named `rows_name`) source rows that are
+// read without idx, the pointers that must be set, the workspace's size and alignment, the grid.  0, or the error.
+template <typename Args, size_t N>
+int check_head(const char* head, const Args& p, const char* rows_name, long long rows, const Required (&required)[N],
+               int extra) {
+  if (p.m < 1) return h12_learn_fail(H12LEARN_E_ARG, "%s: m = %lld (must be >= 1)", head, p.m);
+  if (p.A < 1 || p.A > HEAD_MAX_A)
+    return h12_learn_fail(H12LEARN_E_ARG, "%s: A = %d (1 .. %d)", head, p.A, HEAD_MAX_A);
+  if (p.n_src < 1) return h12_learn_fail(H12LEARN_E_ARG, "%s: n_src = %lld (must be >= 1)", head, p.n_src);
+  if (!p.idx && rows > p.n_src)
+    return h12_learn_fail(H12LEARN_E_ARG, "%s: %s = %lld rows of sources of n_src = %lld without idx", head, rows_name,
+                          rows, p.n_src);
+  for (const Required& q : required)
+    if (!q.ptr) return h12_learn_fail(H12LEARN_E_ARG, "%s: %s is null", head, q.name);
+  const size_t need = workspace_bytes(head, p.m, p.A, extra);
+  if (p.workspace_bytes < need)
+    return h12_learn_fail(H12LEARN_E_ARG, "%s: workspace_bytes = %zu, %zu needed", head, p.workspace_bytes, need);
+  if (((uintptr_t)p.workspace & 7) != 0)
+    return h12_learn_fail(H12LEARN_E_ARG, "%s: workspace is not 8-byte aligned", head);
+  if (head_blocks(p.m) > 0x7fffffffLL) return h12_learn_fail(H12LEARN_E_ARG, "%s: m = %lld exceeds the grid", head, p.m);
+  return H12LEARN_OK;
+}
+
+LossScalars loss_scalars(double clip, double vcoef, double ecoef) {
+  return {(float)(1.0 - clip), (float)(1.0 + clip), (float)clip, (float)vcoef, (float)ecoef};
+}
+
+// a head's rows kernel: 16 lanes per row up to 16 actions, 32 above
+template <typename K, typename... KernelArgs>
+void launch_rows(K rows16, K rows32, int A, long long blocks, hipStream_t s, KernelArgs... args) {
+  hipLaunchKernelGGL(A <= 16 ? rows16 : rows32, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, args...);
+}
 
 }  // namespace
 
@@ -598,64 +607,31 @@ int h12learn_ppo_head_rows(void) { return HEAD_ROWS; }
 
 int h12learn_ppo_head_max_actions(void) { return HEAD_MAX_A; }
 
-size_t h12learn_ppo_head_workspace_bytes(long long m, int A) {
-  if (m < 1) {
-    h12_learn_fail(H12LEARN_E_ARG, "ppo_head_workspace_bytes: m = %lld (must be >= 1)", m);
-    return 0;
-  }
-  if (A < 1 || A > HEAD_MAX_A) {
-    h12_learn_fail(H12LEARN_E_ARG, "ppo_head_workspace_bytes: A = %d (1 .. %d)", A, HEAD_MAX_A);
-    return 0;
-  }
-  return (size_t)head_blocks(m) * (size_t)(HEAD_SC + A) * sizeof(double);
-}
+size_t h12learn_ppo_head_workspace_bytes(long long m, int A) { return workspace_bytes("ppo_head", m, A, 0); }
 
 int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream) {
   if (!args) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: args is null");
   const h12learn_ppo_head_args& p = *args;
-  if (p.m < 1) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld (must be >= 1)", p.m);
+  const Required required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.std_param, "std_param"},
+                               {p.old_log_prob, "old_log_prob"}, {p.advantages, "advantages"}, {p.returns, "returns"},
+                               {p.target_values, "target_values"}, {p.old_mu, "old_mu"}, {p.old_sigma, "old_sigma"},
+                               {p.actions, "actions"}, {p.d_mean, "d_mean"}, {p.d_value, "d_value"},
+                               {p.d_param, "d_param"}, {p.out, "out"}, {p.workspace, "workspace"}};
+  if (const int rc = check_head("ppo_head", p, "B", p.B, required, 0)) return rc;
   if (p.B < 1 || (p.m != p.B && p.m != 2 * p.B))
     return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld is neither B nor 2 B (B = %lld)", p.m, p.B);
-  if (p.A < 1 || p.A > HEAD_MAX_A) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: A = %d (1 .. %d)", p.A, HEAD_MAX_A);
-  if (p.n_src < 1) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: n_src = %lld (must be >= 1)", p.n_src);
-  if (!p.idx && p.B > p.n_src)
-    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: B = %lld rows of sources of n_src = %lld without idx", p.B,
-                          p.n_src);
   if (p.std_kind != H12LEARN_PPO_STD_SCALAR && p.std_kind != H12LEARN_PPO_STD_LOG)
     return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: std_kind = %d (H12LEARN_PPO_STD_SCALAR or _LOG)", p.std_kind);
-  const struct {
-    const void* ptr;
-    const char* name;
-  } required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.std_param, "std_param"}, {p.old_log_prob, "old_log_prob"},
-                  {p.advantages, "advantages"}, {p.returns, "returns"}, {p.target_values, "target_values"},
-                  {p.old_mu, "old_mu"}, {p.old_sigma, "old_sigma"}, {p.actions, "actions"}, {p.d_mean, "d_mean"},
-                  {p.d_value, "d_value"}, {p.d_param, "d_param"}, {p.out, "out"}, {p.workspace, "workspace"}};
-  for (const auto& q : required)
-    if (!q.ptr) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: %s is null", q.name);
   if (!(p.clip_param >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: clip_param = %g (must be >= 0)", p.clip_param);
   if (p.lr && !(p.desired_kl > 0.0))
     return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: desired_kl = %g with lr set (must be > 0)", p.desired_kl);
-  const size_t need = h12learn_ppo_head_workspace_bytes(p.m, p.A);
-  if (p.workspace_bytes < need)
-    return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: workspace_bytes = %zu, %zu needed", p.workspace_bytes, need);
-  if (((uintptr_t)p.workspace & 7) != 0) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: workspace is not 8-byte aligned");
-  const long long blocks = head_blocks(p.m);
-  if (blocks > 0x7fffffffLL) return h12_learn_fail(H12LEARN_E_ARG, "ppo_head: m = %lld exceeds the grid", p.m);
 
-  HeadScalars sc;
-  sc.lo = (float)(1.0 - p.clip_param);
-  sc.hi = (float)(1.0 + p.clip_param);
-  sc.clip = (float)p.clip_param;
-  sc.vcoef = (float)p.value_loss_coef;
-  sc.ecoef = (float)p.entropy_coef;
-  sc.kl_up = (float)(p.desired_kl * 2.0);
-  sc.kl_down = (float)(p.desired_kl / 2.0);
+  const HeadScalars sc = {loss_scalars(p.clip_param, p.value_loss_coef, p.entropy_coef), (float)(p.desired_kl * 2.0),
+                          (float)(p.desired_kl / 2.0)};
+  const long long blocks = head_blocks(p.m);
   hipStream_t s = (hipStream_t)stream;
   double* partial = (double*)p.workspace;
-  if (p.A <= 16)
-    hipLaunchKernelGGL(ppo_head_rows_kernel<16>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc, partial);
-  else
-    hipLaunchKernelGGL(ppo_head_rows_kernel<32>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc, partial);
+  launch_rows(ppo_head_rows_kernel<16>, ppo_head_rows_kernel<32>, p.A, blocks, s, p, sc, partial);
   HEAD_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(ppo_head_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, s, p, sc, (const double*)partial,
                      (int)blocks);
@@ -666,56 +642,26 @@ int h12learn_ppo_head(const h12learn_ppo_head_args* args, void* stream) {
 int h12learn_cleanrl_head_rows(void) { return HEAD_ROWS; }
 
 size_t h12learn_cleanrl_head_workspace_bytes(long long m, int A) {
-  if (m < 1) {
-    h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head_workspace_bytes: m = %lld (must be >= 1)", m);
-    return 0;
-  }
-  if (A < 1 || A > HEAD_MAX_A) {
-    h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head_workspace_bytes: A = %d (1 .. %d)", A, HEAD_MAX_A);
-    return 0;
-  }
-  return (size_t)head_blocks(m) * (size_t)(CLEAN_ADV + CLEAN_SC + A) * sizeof(double);
+  return workspace_bytes("cleanrl_head", m, A, CLEAN_ADV);
 }
 
 int h12learn_cleanrl_head(const h12learn_cleanrl_head_args* args, void* stream) {
   if (!args) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: args is null");
   const h12learn_cleanrl_head_args& p = *args;
-  if (p.m < 1) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld (must be >= 1)", p.m);
+  const Required required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.logstd, "logstd"},
+                               {p.old_log_prob, "old_log_prob"}, {p.advantages, "advantages"},
+                               {p.returns_n, "returns_n"}, {p.values_n, "values_n"}, {p.actions, "actions"},
+                               {p.value_mean, "value_mean"}, {p.value_var, "value_var"}, {p.d_mean, "d_mean"},
+                               {p.d_value, "d_value"}, {p.d_logstd, "d_logstd"}, {p.out, "out"},
+                               {p.workspace, "workspace"}};
+  if (const int rc = check_head("cleanrl_head", p, "m", p.m, required, CLEAN_ADV)) return rc;
   if (p.norm_adv && p.m < 2)
     return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld with norm_adv (the std of one advantage is NaN)", p.m);
-  if (p.A < 1 || p.A > HEAD_MAX_A)
-    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: A = %d (1 .. %d)", p.A, HEAD_MAX_A);
-  if (p.n_src < 1) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: n_src = %lld (must be >= 1)", p.n_src);
-  if (!p.idx && p.m > p.n_src)
-    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld rows of sources of n_src = %lld without idx", p.m,
-                          p.n_src);
-  const struct {
-    const void* ptr;
-    const char* name;
-  } required[] = {{p.mean, "mean"}, {p.value, "value"}, {p.logstd, "logstd"}, {p.old_log_prob, "old_log_prob"},
-                  {p.advantages, "advantages"}, {p.returns_n, "returns_n"}, {p.values_n, "values_n"},
-                  {p.actions, "actions"}, {p.value_mean, "value_mean"}, {p.value_var, "value_var"},
-                  {p.d_mean, "d_mean"}, {p.d_value, "d_value"}, {p.d_logstd, "d_logstd"}, {p.out, "out"},
-                  {p.workspace, "workspace"}};
-  for (const auto& q : required)
-    if (!q.ptr) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: %s is null", q.name);
   if (!(p.clip_coef >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: clip_coef = %g (must be >= 0)", p.clip_coef);
   if (!(p.value_eps >= 0.0)) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: value_eps = %g (must be >= 0)", p.value_eps);
-  const size_t need = h12learn_cleanrl_head_workspace_bytes(p.m, p.A);
-  if (p.workspace_bytes < need)
-    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: workspace_bytes = %zu, %zu needed", p.workspace_bytes, need);
-  if (((uintptr_t)p.workspace & 7) != 0)
-    return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: workspace is not 8-byte aligned");
-  const long long blocks = head_blocks(p.m);
-  if (blocks > 0x7fffffffLL) return h12_learn_fail(H12LEARN_E_ARG, "cleanrl_head: m = %lld exceeds the grid", p.m);
 
-  CleanScalars sc;
-  sc.lo = (float)(1.0 - p.clip_coef);
-  sc.hi = (float)(1.0 + p.clip_coef);
-  sc.clip = (float)p.clip_coef;
-  sc.vcoef = (float)p.vf_coef;
-  sc.ecoef = (float)p.ent_coef;
-  sc.veps = (float)p.value_eps;
+  const CleanScalars sc = {loss_scalars(p.clip_coef, p.vf_coef, p.ent_coef), (float)p.value_eps};
+  const long long blocks = head_blocks(p.m);
   hipStream_t s = (hipStream_t)stream;
   double* apart = (double*)p.workspace;
   double* partial = apart + (size_t)blocks * CLEAN_ADV;
@@ -723,12 +669,8 @@ int h12learn_cleanrl_head(const h12learn_cleanrl_head_args* args, void* stream) 
     hipLaunchKernelGGL(cleanrl_adv_kernel, dim3((unsigned)blocks), dim3(64), 0, s, p, apart);
     HEAD_HIP_TRY(hipGetLastError());
   }
-  if (p.A <= 16)
-    hipLaunchKernelGGL(cleanrl_head_rows_kernel<16>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc,
-                       (const double*)apart, partial, (int)blocks);
-  else
-    hipLaunchKernelGGL(cleanrl_head_rows_kernel<32>, dim3((unsigned)blocks), dim3(HEAD_WAVES * 64), 0, s, p, sc,
-                       (const double*)apart, partial, (int)blocks);
+  launch_rows(cleanrl_head_rows_kernel<16>, cleanrl_head_rows_kernel<32>, p.A, blocks, s, p, sc, (const double*)apart,
+              partial, (int)blocks);
   HEAD_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(cleanrl_head_fold_kernel, dim3(1), dim3(FOLD_THREADS), 0, s, p, sc, (const double*)partial,
                      (int)blocks);
@@ -737,3 +679,4 @@ int h12learn_cleanrl_head(const h12learn_cleanrl_head_args* args, void* stream) 
 }
 
 }  // extern "C"
+

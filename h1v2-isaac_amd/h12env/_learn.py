@@ -371,7 +371,49 @@ def mlp_backward(desc: MlpDesc, packed_t: torch.Tensor, dy: torch.Tensor, hs, ne
     return dzs, dbs, dx
 
 
-# ---- fused PPO loss head (csrc/h12_ppo_head.hip)
+# ---- fused loss heads (csrc/h12_ppo_head.hip): what ppo_head and cleanrl_head check and allocate alike
+def _head_check(head: str, mean, value, param, param_name: str, per_row, idx, idx_rows, stats_accum, n_stats: int):
+    """The networks' outputs (mean [m][A], value of m elements, the std parameter of A), the per-row rollout tensors
+    (name, tensor; n_src elements each), idx (None, or ``idx_rows`` int64 entries; None: m) and stats_accum (None, or at
+    least n_stats floats).  Returns (m, A, n_src)."""
+    _f32(mean, "mean"), _f32(value, "value"), _f32(param, param_name)
+    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 1:
+        raise ValueError(f"{head}: mean {tuple(mean.shape)} is not (m >= 1, A >= 1)")
+    m, A = mean.shape
+    if value.numel() != m or param.numel() != A:
+        raise ValueError(f"{head}: value has {value.numel()} and {param_name} {param.numel()} elements for mean "
+                         f"{tuple(mean.shape)}")
+    n_src = per_row[0][1].numel()
+    for name, t in per_row:
+        if _f32(t, name).numel() != n_src:
+            raise ValueError(f"{head}: {name} must have {n_src} elements")
+    rows = m if idx_rows is None else idx_rows
+    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
+                                and idx.shape == (rows,)):
+        raise ValueError(f"{head}: idx must be a contiguous int64 CUDA tensor of {rows} entries")
+    if stats_accum is not None and _f32(stats_accum, "stats_accum").numel() < n_stats:
+        raise ValueError(f"{head}: stats_accum must have at least {n_stats} elements")
+    return m, A, n_src
+
+
+def _head_outputs(m: int, A: int, dev):
+    """(d_mean [m][A], d_value [m], the std parameter's gradient [A], out [5]), uninitialised."""
+    return (torch.empty((m, A), dtype=torch.float32, device=dev), torch.empty(m, dtype=torch.float32, device=dev),
+            torch.empty(A, dtype=torch.float32, device=dev), torch.empty(5, dtype=torch.float32, device=dev))
+
+
+def _head_fill(a, mean, value, idx, old_log_prob, advantages, actions, outputs, stats_accum, ws, nbytes: int):
+    """The fields the two argument structs name alike (the std parameter and its gradient are set by the caller)."""
+    a.m, a.A = mean.shape
+    a.n_src = old_log_prob.numel()
+    a.mean, a.value = mean.data_ptr(), value.data_ptr()
+    a.idx = None if idx is None else idx.data_ptr()
+    a.old_log_prob, a.advantages, a.actions = old_log_prob.data_ptr(), advantages.data_ptr(), actions.data_ptr()
+    a.d_mean, a.d_value, a.out = outputs[0].data_ptr(), outputs[1].data_ptr(), outputs[3].data_ptr()
+    a.stats_accum = None if stats_accum is None else stats_accum.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+
+
 def ppo_head_rows() -> int:
     return learn_library().h12learn_ppo_head_rows()
 
@@ -390,61 +432,37 @@ def ppo_head(mean: torch.Tensor, value: torch.Tensor, std_param: torch.Tensor, s
     ``actions_direct``).  ``lr`` (a device scalar; needs desired_kl) and ``stats_accum`` (3 floats) are updated in place
     when given.  include/h12learn.h has the formulae."""
     lib = learn_library()
-    _f32(mean, "mean"), _f32(value, "value"), _f32(std_param, "std_param")
-    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 1:
-        raise ValueError(f"ppo_head: mean {tuple(mean.shape)} is not (m >= 1, A >= 1)")
-    m, A = mean.shape
-    dev = mean.device
-    if value.numel() != m or std_param.numel() != A:
-        raise ValueError(f"ppo_head: value has {value.numel()} and std_param {std_param.numel()} elements for mean "
-                         f"{tuple(mean.shape)}")
     B = int(n_rows)
-    n_src = old_log_prob.numel()
-    for name, t in (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns", returns),
-                    ("target_values", target_values)):
-        if _f32(t, name).numel() != n_src:
-            raise ValueError(f"ppo_head: {name} must have {n_src} elements")
+    m, A, n_src = _head_check("ppo_head", mean, value, std_param, "std_param",
+                              (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns", returns),
+                               ("target_values", target_values)), idx, B, stats_accum, 3)
     for name, t in (("old_mu", old_mu), ("old_sigma", old_sigma)):
         if _f32(t, name).shape != (n_src, A):
             raise ValueError(f"ppo_head: {name} must be ({n_src}, {A})")
     if _f32(actions, "actions").shape != ((m, A) if actions_direct else (n_src, A)):
         raise ValueError(f"ppo_head: actions {tuple(actions.shape)} for m = {m}, n_src = {n_src}, "
                          f"actions_direct = {bool(actions_direct)}")
-    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
-                                and idx.shape == (B,)):
-        raise ValueError(f"ppo_head: idx must be a contiguous int64 CUDA tensor of {B} entries")
     if lr is not None and (_f32(lr, "lr").numel() != 1 or desired_kl is None):
         raise ValueError("ppo_head: lr must be one float32 element and needs desired_kl")
-    if stats_accum is not None and _f32(stats_accum, "stats_accum").numel() < 3:
-        raise ValueError("ppo_head: stats_accum must have at least 3 elements")
     nbytes = lib.h12learn_ppo_head_workspace_bytes(m, A)
     if nbytes == 0:
         _check(lib, -1, "h12learn_ppo_head_workspace_bytes")
-    d_mean = torch.empty((m, A), dtype=torch.float32, device=dev)
-    d_value = torch.empty(m, dtype=torch.float32, device=dev)
-    d_param = torch.empty(A, dtype=torch.float32, device=dev)
-    out = torch.empty(5, dtype=torch.float32, device=dev)
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    outputs = _head_outputs(m, A, mean.device)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=mean.device)  # a fresh one per call
     a = PpoHeadArgs()
-    a.m, a.B, a.n_src, a.A = m, B, n_src, A
-    a.std_kind, a.actions_direct = int(std_kind), int(bool(actions_direct))
+    _head_fill(a, mean, value, idx, old_log_prob, advantages, actions, outputs, stats_accum, ws, nbytes)
+    a.B, a.std_kind, a.actions_direct = B, int(std_kind), int(bool(actions_direct))
     a.use_clipped_value_loss = int(bool(use_clipped_value_loss))
-    a.mean, a.value, a.std_param = mean.data_ptr(), value.data_ptr(), std_param.data_ptr()
-    a.idx = None if idx is None else idx.data_ptr()
-    a.old_log_prob, a.advantages, a.returns = old_log_prob.data_ptr(), advantages.data_ptr(), returns.data_ptr()
-    a.target_values, a.old_mu, a.old_sigma = target_values.data_ptr(), old_mu.data_ptr(), old_sigma.data_ptr()
-    a.actions = actions.data_ptr()
+    a.std_param, a.d_param = std_param.data_ptr(), outputs[2].data_ptr()
+    a.returns, a.target_values = returns.data_ptr(), target_values.data_ptr()
+    a.old_mu, a.old_sigma = old_mu.data_ptr(), old_sigma.data_ptr()
     a.clip_param, a.value_loss_coef, a.entropy_coef = float(clip_param), float(value_loss_coef), float(entropy_coef)
     a.desired_kl = 0.0 if desired_kl is None else float(desired_kl)
-    a.d_mean, a.d_value, a.d_param, a.out = d_mean.data_ptr(), d_value.data_ptr(), d_param.data_ptr(), out.data_ptr()
     a.lr = None if lr is None else lr.data_ptr()
-    a.stats_accum = None if stats_accum is None else stats_accum.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-    _check(lib, lib.h12learn_ppo_head(C.byref(a), _stream(dev)), "h12learn_ppo_head")
-    return d_mean, d_value, d_param, out
+    _check(lib, lib.h12learn_ppo_head(C.byref(a), _stream(mean.device)), "h12learn_ppo_head")
+    return outputs
 
 
-# ---- fused CleanRL loss head (csrc/h12_ppo_head.hip)
 def cleanrl_head_rows() -> int:
     return learn_library().h12learn_cleanrl_head_rows()
 
@@ -476,47 +494,27 @@ def cleanrl_head(mean: torch.Tensor, value: torch.Tensor, logstd: torch.Tensor, 
     ``stats_accum`` (5 floats) is updated in place when given; ``workspace`` defaults to the cached one.
     include/h12learn.h has the formulae."""
     lib = learn_library()
-    _f32(mean, "mean"), _f32(value, "value"), _f32(logstd, "logstd")
-    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 1:
-        raise ValueError(f"cleanrl_head: mean {tuple(mean.shape)} is not (m >= 1, A >= 1)")
-    m, A = mean.shape
-    dev = mean.device
-    if value.numel() != m or logstd.numel() != A:
-        raise ValueError(f"cleanrl_head: value has {value.numel()} and logstd {logstd.numel()} elements for mean "
-                         f"{tuple(mean.shape)}")
-    n_src = old_log_prob.numel()
-    for name, t in (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns_n", returns_n),
-                    ("values_n", values_n)):
-        if _f32(t, name).numel() != n_src:
-            raise ValueError(f"cleanrl_head: {name} must have {n_src} elements")
+    m, A, n_src = _head_check("cleanrl_head", mean, value, logstd, "logstd",
+                              (("old_log_prob", old_log_prob), ("advantages", advantages), ("returns_n", returns_n),
+                               ("values_n", values_n)), idx, None, stats_accum, 5)
     if _f32(actions, "actions").shape != (n_src, A):
         raise ValueError(f"cleanrl_head: actions {tuple(actions.shape)} must be ({n_src}, {A})")
     for name, t in (("value_mean", value_mean), ("value_var", value_var)):
         if _f32(t, name).numel() != 1:
             raise ValueError(f"cleanrl_head: {name} must be one float32 element")
-    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous()
-                                and idx.shape == (m,)):
-        raise ValueError(f"cleanrl_head: idx must be a contiguous int64 CUDA tensor of {m} entries")
-    if stats_accum is not None and _f32(stats_accum, "stats_accum").numel() < 5:
-        raise ValueError("cleanrl_head: stats_accum must have at least 5 elements")
-    ws = cleanrl_head_workspace(m, A, dev) if workspace is None else workspace
+    ws = cleanrl_head_workspace(m, A, mean.device) if workspace is None else workspace
     if not (ws.is_cuda and ws.is_contiguous()):
         raise ValueError("cleanrl_head: workspace must be a contiguous CUDA tensor")
-    d_mean = torch.empty((m, A), dtype=torch.float32, device=dev)
-    d_value = torch.empty(m, dtype=torch.float32, device=dev)
-    d_logstd = torch.empty(A, dtype=torch.float32, device=dev)
-    out = torch.empty(5, dtype=torch.float32, device=dev)
+    outputs = _head_outputs(m, A, mean.device)
     a = CleanRlHeadArgs()
-    a.m, a.n_src, a.A = m, n_src, A
+    _head_fill(a, mean, value, idx, old_log_prob, advantages, actions, outputs, stats_accum, ws,
+               ws.numel() * ws.element_size())
     a.norm_adv, a.clip_vloss = int(bool(norm_adv)), int(bool(clip_vloss))
-    a.mean, a.value, a.logstd = mean.data_ptr(), value.data_ptr(), logstd.data_ptr()
-    a.idx = None if idx is None else idx.data_ptr()
-    a.old_log_prob, a.advantages = old_log_prob.data_ptr(), advantages.data_ptr()
-    a.returns_n, a.values_n, a.actions = returns_n.data_ptr(), values_n.data_ptr(), actions.data_ptr()
+    a.logstd, a.d_logstd = logstd.data_ptr(), outputs[2].data_ptr()
+    a.returns_n, a.values_n = returns_n.data_ptr(), values_n.data_ptr()
     a.value_mean, a.value_var, a.value_eps = value_mean.data_ptr(), value_var.data_ptr(), float(value_eps)
     a.clip_coef, a.ent_coef, a.vf_coef = float(clip_coef), float(ent_coef), float(vf_coef)
-    a.d_mean, a.d_value, a.d_logstd, a.out = d_mean.data_ptr(), d_value.data_ptr(), d_logstd.data_ptr(), out.data_ptr()
-    a.stats_accum = None if stats_accum is None else stats_accum.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    _check(lib, lib.h12learn_cleanrl_head(C.byref(a), _stream(dev)), "h12learn_cleanrl_head")
-    return d_mean, d_value, d_logstd, out
+    _check(lib, lib.h12learn_cleanrl_head(C.byref(a), _stream(mean.device)), "h12learn_cleanrl_head")
+    return outputs
+
+

@@ -566,14 +566,39 @@ class PPO:
             g.copy_(flat[off:off + n].view_as(g))
             off += n
 
+    def _adapt_lr(self, kl_mean: torch.Tensor):
+        """rsl_rl's KL-adaptive schedule on a minibatch's mean KL (averaged over the ranks first): on the device tensor
+        the fused optimizer reads, without a host sync, or on the host learning rate."""
+        with torch.no_grad():
+            if self.shard.world > 1:
+                D.all_reduce(kl_mean, op=dist.ReduceOp.SUM)
+                kl_mean /= self.shard.world
+            if self._lr_t is not None:
+                lr = self._lr_t
+                up = kl_mean > self.desired_kl * 2.0
+                down = (kl_mean > 0.0) & (kl_mean < self.desired_kl / 2.0)
+                self._lr_t.copy_(torch.where(up, torch.clamp(lr / 1.5, min=1e-5),
+                                             torch.where(down, torch.clamp(lr * 1.5, max=1e-2), lr)))
+            else:
+                k = kl_mean.item()
+                if k > self.desired_kl * 2.0:
+                    self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+                elif 0.0 < k < self.desired_kl / 2.0:
+                    self.learning_rate = min(1e-2, self.learning_rate * 1.5)
+                for g in self.optimizer.param_groups:
+                    g["lr"] = self.learning_rate
+
     def _minibatch(self, b: dict, idx: torch.Tensor, stats: torch.Tensor):
         """One PPO minibatch update (rsl_rl ppo.py update loop body): gather, forward, KL-adaptive learning
         rate, clipped surrogate + clipped value loss, backward, (all-reduce), grad clip, Adam, statistics.
-        Host-sync free on the fused path, so it is also the body of the captured HIP graph."""
-        if self.fused_loss:
-            return self._minibatch_fused_loss(b, idx, stats)
-        world = self.shard.world
+        Host-sync free on the fused path, so it is also the body of the captured HIP graph.
+
+        With fused_loss only the observations are gathered here (and the actions where they are mirrored); everything
+        from get_actions_log_prob to loss is one PPOHead node, which on a single CUDA rank also applies the adaptive
+        schedule to _lr_t and, without symmetry, adds the statistics."""
         sym = self.symmetry
+        fused = self.fused_loss
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         aug = sym is not None and sym["use_data_augmentation"]
         n_orig = idx.shape[0]
         if aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
@@ -583,17 +608,18 @@ class PPO:
         else:
             obs = b["observations"][idx]
             critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
-            actions = b["actions"][idx]
-        target_values = b["values"][idx]
-        advantages = b["advantages"][idx]
-        returns = b["returns"][idx]
-        old_log_prob = b["actions_log_prob"][idx]
-        old_mu, old_sigma = b["mu"][idx], b["sigma"][idx]
-        if self.normalize_advantage_per_mini_batch:
-            advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-8)
-        if aug:  # the mirrored samples keep their originals' statistics (normalised above on the original batch)
-            old_log_prob, target_values, advantages, returns = (torch.cat([t, t]) for t in
-                                                                (old_log_prob, target_values, advantages, returns))
+            actions = b["actions"] if fused else b["actions"][idx]  # the head gathers its rows itself
+        if not fused:
+            target_values = b["values"][idx]
+            advantages = b["advantages"][idx]
+            returns = b["returns"][idx]
+            old_log_prob = b["actions_log_prob"][idx]
+            old_mu, old_sigma = b["mu"][idx], b["sigma"][idx]
+            if self.normalize_advantage_per_mini_batch:
+                advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-8)
+            if aug:  # the mirrored samples keep their originals' statistics (normalised above on the original batch)
+                old_log_prob, target_values, advantages, returns = (torch.cat([t, t]) for t in
+                                                                    (old_log_prob, target_values, advantages, returns))
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
                             enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
             self.policy.update_distribution(obs)  # rsl_rl calls act(); the sample itself is unused
@@ -601,44 +627,43 @@ class PPO:
         if self.precision == "bf16":  # distribution statistics in fp32
             self.policy.distribution = Normal(self.policy.distribution.mean.float(),
                                               self.policy.distribution.stddev.float())
-        log_prob = self.policy.get_actions_log_prob(actions)
-        mu, sigma, entropy = self.policy.action_mean, self.policy.action_std, self.policy.entropy
-        if aug:  # the KL of the schedule and the entropy bonus are those of the original samples
-            mu, sigma, entropy = mu[:n_orig], sigma[:n_orig], entropy[:n_orig]
-        if self.desired_kl is not None and self.schedule == "adaptive":
-            with torch.no_grad():
-                kl = torch.sum(torch.log(sigma / old_sigma + 1e-5)
-                               + (old_sigma.square() + (old_mu - mu).square()) / (2.0 * sigma.square()) - 0.5, dim=-1)
-                kl_mean = kl.mean()
-                if world > 1:
-                    D.all_reduce(kl_mean, op=dist.ReduceOp.SUM)
-                    kl_mean /= world
-                if self._lr_t is not None:
-                    # rsl_rl's schedule on the device tensor the fused optimizer reads
-                    lr = self._lr_t
-                    up = kl_mean > self.desired_kl * 2.0
-                    down = (kl_mean > 0.0) & (kl_mean < self.desired_kl / 2.0)
-                    self._lr_t.copy_(torch.where(up, torch.clamp(lr / 1.5, min=1e-5),
-                                                 torch.where(down, torch.clamp(lr * 1.5, max=1e-2), lr)))
-                else:
-                    k = kl_mean.item()
-                    if k > self.desired_kl * 2.0:
-                        self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-                    elif 0.0 < k < self.desired_kl / 2.0:
-                        self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-                    for g in self.optimizer.param_groups:
-                        g["lr"] = self.learning_rate
-        ratio = torch.exp(log_prob - old_log_prob.squeeze(-1))
-        adv = advantages.squeeze(-1)
-        surrogate = -adv * ratio
-        surrogate_clipped = -adv * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
-        surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
-        if self.use_clipped_value_loss:
-            v_clipped = target_values + (value - target_values).clamp(-self.clip_param, self.clip_param)
-            value_loss = torch.max((value - returns).square(), (v_clipped - returns).square()).mean()
+        if fused:
+            from .ppo_head import HeadInputs, PPOHead
+
+            mean = self.policy.action_mean
+            kind = self.policy.noise_std_type
+            head = HeadInputs(idx=idx, old_log_prob=b["actions_log_prob"], advantages=b["advantages"],
+                              returns=b["returns"], target_values=b["values"], old_mu=b["mu"], old_sigma=b["sigma"],
+                              actions=actions, actions_direct=aug, std_kind=kind, clip_param=self.clip_param,
+                              value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
+                              use_clipped_value_loss=self.use_clipped_value_loss,
+                              lr=self._lr_t if mean.is_cuda and adaptive and self.shard.world == 1 else None,
+                              desired_kl=self.desired_kl, stats_accum=stats if mean.is_cuda and sym is None else None)
+            loss, out = PPOHead.apply(mean, value, self.policy.std if kind == "scalar" else self.policy.log_std, head)
+            if adaptive and head.lr is None:  # CPU, or several ranks: the KL from the head
+                self._adapt_lr(out[3].clone())
         else:
-            value_loss = (returns - value).square().mean()
-        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+            log_prob = self.policy.get_actions_log_prob(actions)
+            mu, sigma, entropy = self.policy.action_mean, self.policy.action_std, self.policy.entropy
+            if aug:  # the KL of the schedule and the entropy bonus are those of the original samples
+                mu, sigma, entropy = mu[:n_orig], sigma[:n_orig], entropy[:n_orig]
+            if adaptive:
+                with torch.no_grad():
+                    kl = torch.sum(torch.log(sigma / old_sigma + 1e-5)
+                                   + (old_sigma.square() + (old_mu - mu).square()) / (2.0 * sigma.square()) - 0.5,
+                                   dim=-1)
+                    self._adapt_lr(kl.mean())
+            ratio = torch.exp(log_prob - old_log_prob.squeeze(-1))
+            adv = advantages.squeeze(-1)
+            surrogate = -adv * ratio
+            surrogate_clipped = -adv * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
+            surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
+            if self.use_clipped_value_loss:
+                v_clipped = target_values + (value - target_values).clamp(-self.clip_param, self.clip_param)
+                value_loss = torch.max((value - returns).square(), (v_clipped - returns).square()).mean()
+            else:
+                value_loss = (returns - value).square().mean()
+            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
         if sym is not None:
             symmetry_loss = self._symmetry_loss(obs, aug, n_orig)
             if sym["use_mirror_loss"]:
@@ -648,82 +673,12 @@ class PPO:
         self._allreduce_grads()
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         self.optimizer.step()
-        if sym is not None:
-            stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach(),
-                                  symmetry_loss.detach()])
+        if fused:  # value loss, surrogate, entropy: from the head, unless it has added them to stats itself
+            parts = [out[1], out[0], out[2]] if head.stats_accum is None else None
         else:
-            stats += torch.stack([value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()])
-
-    def _minibatch_fused_loss(self, b: dict, idx: torch.Tensor, stats: torch.Tensor):
-        """_minibatch with fused_loss: only the observations are gathered (and the actions where they are mirrored);
-        everything from get_actions_log_prob to loss is one PPOHead node, which on a single CUDA rank also applies
-        the adaptive schedule to _lr_t and, without symmetry, adds the statistics."""
-        from .ppo_head import HeadInputs, PPOHead
-
-        world = self.shard.world
-        sym = self.symmetry
-        aug = sym is not None and sym["use_data_augmentation"]
-        n_orig = idx.shape[0]
-        if aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
-            obs, actions = self._augment(b["observations"], b["actions"], idx, "policy")
-            critic_obs = (self._augment(b["privileged_observations"], None, idx, "critic")[0]
-                          if "privileged_observations" in b else obs)
-        else:
-            obs = b["observations"][idx]
-            critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
-            actions = b["actions"]  # the head gathers its rows
-        with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
-                            enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
-            self.policy.update_distribution(obs)
-            value = self.policy.evaluate(critic_obs).float()
-        if self.precision == "bf16":  # distribution statistics in fp32
-            self.policy.distribution = Normal(self.policy.distribution.mean.float(),
-                                              self.policy.distribution.stddev.float())
-        mean = self.policy.action_mean
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        on_device = mean.is_cuda
-        kind = self.policy.noise_std_type
-        head = HeadInputs(idx=idx, old_log_prob=b["actions_log_prob"], advantages=b["advantages"],
-                          returns=b["returns"], target_values=b["values"], old_mu=b["mu"], old_sigma=b["sigma"],
-                          actions=actions, actions_direct=aug, std_kind=kind, clip_param=self.clip_param,
-                          value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
-                          use_clipped_value_loss=self.use_clipped_value_loss,
-                          lr=self._lr_t if on_device and adaptive and world == 1 else None,
-                          desired_kl=self.desired_kl, stats_accum=stats if on_device and sym is None else None)
-        loss, out = PPOHead.apply(mean, value, self.policy.std if kind == "scalar" else self.policy.log_std, head)
-        if adaptive and head.lr is None:  # CPU, or several ranks: the KL from the head, the schedule as in _minibatch
-            with torch.no_grad():
-                kl_mean = out[3].clone()
-                if world > 1:
-                    D.all_reduce(kl_mean, op=dist.ReduceOp.SUM)
-                    kl_mean /= world
-                if self._lr_t is not None:
-                    lr = self._lr_t
-                    up = kl_mean > self.desired_kl * 2.0
-                    down = (kl_mean > 0.0) & (kl_mean < self.desired_kl / 2.0)
-                    self._lr_t.copy_(torch.where(up, torch.clamp(lr / 1.5, min=1e-5),
-                                                 torch.where(down, torch.clamp(lr * 1.5, max=1e-2), lr)))
-                else:
-                    k = kl_mean.item()
-                    if k > self.desired_kl * 2.0:
-                        self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-                    elif 0.0 < k < self.desired_kl / 2.0:
-                        self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-                    for g in self.optimizer.param_groups:
-                        g["lr"] = self.learning_rate
-        if sym is not None:
-            symmetry_loss = self._symmetry_loss(obs, aug, n_orig)
-            if sym["use_mirror_loss"]:
-                loss = loss + sym["mirror_loss_coeff"] * symmetry_loss
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self._allreduce_grads()
-        nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
-        self.optimizer.step()
-        if sym is not None:
-            stats += torch.stack([out[1], out[0], out[2], symmetry_loss.detach()])
-        elif head.stats_accum is None:
-            stats += torch.stack([out[1], out[0], out[2]])
+            parts = [value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()]
+        if parts is not None:
+            stats += torch.stack(parts + ([symmetry_loss.detach()] if sym is not None else []))
 
     def _augment(self, obs, actions, idx, obs_type):
         """data_augmentation_func on the rows ``idx``.  h12env.symmetry.augment takes the index itself: gather, mirror

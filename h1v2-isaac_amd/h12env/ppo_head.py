@@ -95,26 +95,23 @@ def torch_head(mean, value, std_param, h: HeadInputs):
     return loss, out
 
 
-class PPOHead(torch.autograd.Function):
-    """(loss, out) = PPOHead.apply(mean [m][A], value [m][1], std_param [A], HeadInputs).  ``out`` carries no
-    gradient; the backward returns the three gradients the forward computed, scaled by the incoming gradient."""
+class _Head(torch.autograd.Function):
+    """The autograd node both heads are.  A head supplies ``device(mean, value, param, h)``, the HIP call, returning
+    (d_mean, d_value, d_param, out, index of the loss in out), and ``restated(mean, value, param, h)``, its torch
+    restatement looked up on this module when called, returning (loss, out).  The forward runs ``device`` on CUDA tensors
+    and ``restated``, differentiated under enable_grad, on CPU tensors; it saves the three gradients and returns
+    (loss, out) with ``out`` non-differentiable.  The backward scales the saved gradients by the incoming one."""
 
-    @staticmethod
-    def forward(ctx, mean, value, std_param, h: HeadInputs):
+    @classmethod
+    def forward(cls, ctx, mean, value, param, h):
         if mean.is_cuda:
-            n = h.idx.shape[0]
-            flat = lambda t: t.reshape(-1)  # noqa: E731  ([n_src][1] storage columns; contiguous views)
-            d_mean, d_value, d_param, out = _learn.ppo_head(
-                mean, value, std_param, STD_KINDS[h.std_kind], h.idx, n, flat(h.old_log_prob), flat(h.advantages),
-                flat(h.returns), flat(h.target_values), h.old_mu, h.old_sigma, h.actions, h.actions_direct,
-                h.clip_param, h.value_loss_coef, h.entropy_coef, h.use_clipped_value_loss, lr=h.lr,
-                desired_kl=h.desired_kl, stats_accum=h.stats_accum)
-            loss = out[4].clone()
-            d_value = d_value.view_as(value)
+            d_mean, d_value, d_param, out, i_loss = cls.device(mean, value, param, h)
+            loss = out[i_loss].clone()
+            d_value, d_param = d_value.view_as(value), d_param.view_as(param)
         else:
-            leaves = [t.detach().requires_grad_(True) for t in (mean, value, std_param)]
+            leaves = [t.detach().requires_grad_(True) for t in (mean, value, param)]
             with torch.enable_grad():
-                loss, out = torch_head(*leaves, h)
+                loss, out = cls.restated(*leaves, h)
                 d_mean, d_value, d_param = torch.autograd.grad(loss, leaves)
             loss = loss.detach()
         ctx.save_for_backward(d_mean, d_value, d_param)
@@ -126,6 +123,24 @@ class PPOHead(torch.autograd.Function):
     def backward(ctx, g, _g_out):
         d_mean, d_value, d_param = ctx.saved_tensors
         return g * d_mean, g * d_value, g * d_param, None
+
+
+class PPOHead(_Head):
+    """(loss, out) = PPOHead.apply(mean [m][A], value [m][1], std_param [A], HeadInputs).  ``out`` carries no
+    gradient; the backward returns the three gradients the forward computed, scaled by the incoming gradient."""
+
+    @staticmethod
+    def device(mean, value, std_param, h: HeadInputs):
+        flat = lambda t: t.reshape(-1)  # noqa: E731  ([n_src][1] storage columns; contiguous views)
+        return (*_learn.ppo_head(
+            mean, value, std_param, STD_KINDS[h.std_kind], h.idx, h.idx.shape[0], flat(h.old_log_prob),
+            flat(h.advantages), flat(h.returns), flat(h.target_values), h.old_mu, h.old_sigma, h.actions,
+            h.actions_direct, h.clip_param, h.value_loss_coef, h.entropy_coef, h.use_clipped_value_loss, lr=h.lr,
+            desired_kl=h.desired_kl, stats_accum=h.stats_accum), 4)
+
+    @staticmethod
+    def restated(mean, value, std_param, h: HeadInputs):
+        return torch_head(mean, value, std_param, h)
 
 
 # ---------------------------------------------------------------------------------------------- CleanRL
@@ -192,32 +207,18 @@ def torch_cleanrl_head(mean, value, logstd, h: CleanRLInputs):
     return loss, out
 
 
-class CleanRLHead(torch.autograd.Function):
+class CleanRLHead(_Head):
     """(loss, out) = CleanRLHead.apply(mean [m][A], value [m][1], actor_logstd [1][A], CleanRLInputs).  ``out`` carries
     no gradient; the backward returns the three gradients the forward computed, scaled by the incoming gradient."""
 
     @staticmethod
-    def forward(ctx, mean, value, logstd, h: CleanRLInputs):
-        if mean.is_cuda:
-            rms = h.value_rms
-            d_mean, d_value, d_logstd, out = _learn.cleanrl_head(
-                mean, value, logstd, h.idx, h.old_log_prob, h.advantages, h.returns_n, h.values_n, h.actions,
-                rms.running_mean, rms.running_var, rms.epsilon, h.clip_coef, h.ent_coef, h.vf_coef, h.norm_adv,
-                h.clip_vloss, stats_accum=h.stats_accum)
-            loss = out[3].clone()
-            d_value, d_logstd = d_value.view_as(value), d_logstd.view_as(logstd)
-        else:
-            leaves = [t.detach().requires_grad_(True) for t in (mean, value, logstd)]
-            with torch.enable_grad():
-                loss, out = torch_cleanrl_head(*leaves, h)
-                d_mean, d_value, d_logstd = torch.autograd.grad(loss, leaves)
-            loss = loss.detach()
-        ctx.save_for_backward(d_mean, d_value, d_logstd)
-        ctx.mark_non_differentiable(out)
-        return loss, out
+    def device(mean, value, logstd, h: CleanRLInputs):
+        rms = h.value_rms
+        return (*_learn.cleanrl_head(
+            mean, value, logstd, h.idx, h.old_log_prob, h.advantages, h.returns_n, h.values_n, h.actions,
+            rms.running_mean, rms.running_var, rms.epsilon, h.clip_coef, h.ent_coef, h.vf_coef, h.norm_adv,
+            h.clip_vloss, stats_accum=h.stats_accum), 3)
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, g, _g_out):
-        d_mean, d_value, d_logstd = ctx.saved_tensors
-        return g * d_mean, g * d_value, g * d_logstd, None
+    def restated(mean, value, logstd, h: CleanRLInputs):
+        return torch_cleanrl_head(mean, value, logstd, h)

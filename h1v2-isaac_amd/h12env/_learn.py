@@ -17,7 +17,8 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_mlp_forward_train", "h12learn_mlp_backward_workspace_bytes", "h12learn_mlp_backward",
                  "h12learn_ppo_head_rows", "h12learn_ppo_head_max_actions", "h12learn_ppo_head_workspace_bytes",
                  "h12learn_ppo_head", "h12learn_cleanrl_head_rows", "h12learn_cleanrl_head_workspace_bytes",
-                 "h12learn_cleanrl_head", "h12learn_last_error"]
+                 "h12learn_cleanrl_head", "h12learn_lstm_max_hidden", "h12learn_lstm_packed_bytes",
+                 "h12learn_lstm_pack", "h12learn_lstm_step", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -34,6 +35,28 @@ class MlpDesc(C.Structure):
     """h12learn_mlp_desc"""
     _fields_ = [("n_nets", C.c_int), ("d_in", C.c_int), ("norm_kind", C.c_int), ("norm_eps", C.c_float),
                 ("norm_mean", C.c_void_p), ("norm_scale", C.c_void_p), ("nets", MlpNet * MLP_MAX_NETS)]
+
+
+LSTM_MAX_NETS = 2
+
+
+class LstmCell(C.Structure):
+    """h12learn_lstm_cell"""
+    _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p)]
+
+
+class LstmDesc(C.Structure):
+    """h12learn_lstm_desc"""
+    _fields_ = [("d_in", C.c_int), ("hidden", C.c_int), ("norm_kind", C.c_int), ("norm_eps", C.c_float),
+                ("norm_mean", C.c_void_p), ("norm_scale", C.c_void_p), ("cells", LstmCell * LSTM_MAX_NETS),
+                ("mlp", MlpDesc)]
+
+
+class LstmIo(C.Structure):
+    """h12learn_lstm_io"""
+    _fields_ = [("x", C.c_void_p), ("reset", C.c_void_p), ("n", C.c_longlong), ("h_in", C.c_void_p * LSTM_MAX_NETS),
+                ("c_in", C.c_void_p * LSTM_MAX_NETS), ("h_out", C.c_void_p * LSTM_MAX_NETS),
+                ("c_out", C.c_void_p * LSTM_MAX_NETS), ("y", C.c_void_p * LSTM_MAX_NETS)]
 
 
 PPO_STD_SCALAR, PPO_STD_LOG = 0, 1
@@ -125,6 +148,14 @@ def learn_library():
     lib.h12learn_cleanrl_head_workspace_bytes.restype = C.c_size_t
     lib.h12learn_cleanrl_head.argtypes = [C.POINTER(CleanRlHeadArgs), vp]
     lib.h12learn_cleanrl_head.restype = C.c_int
+    lib.h12learn_lstm_max_hidden.argtypes = []
+    lib.h12learn_lstm_max_hidden.restype = C.c_int
+    lib.h12learn_lstm_packed_bytes.argtypes = [C.POINTER(LstmDesc)]
+    lib.h12learn_lstm_packed_bytes.restype = C.c_size_t
+    lib.h12learn_lstm_pack.argtypes = [C.POINTER(LstmDesc), vp, vp]
+    lib.h12learn_lstm_pack.restype = C.c_int
+    lib.h12learn_lstm_step.argtypes = [C.POINTER(LstmDesc), vp, C.POINTER(LstmIo), vp]
+    lib.h12learn_lstm_step.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -369,6 +400,93 @@ def mlp_backward(desc: MlpDesc, packed_t: torch.Tensor, dy: torch.Tensor, hs, ne
                                           arr(dbs), None if dx is None else dx.data_ptr(), ws.data_ptr(), nbytes,
                                           _stream(dev)), "h12learn_mlp_backward")
     return dzs, dbs, dx
+
+
+# ---- fused recurrent policy step (csrc/h12_policy_rnn.hip): LSTM cell + MLP of up to 2 networks over one input
+def lstm_max_hidden() -> int:
+    return learn_library().h12learn_lstm_max_hidden()
+
+
+def lstm_desc(cells, nets, norm_kind: int = MLP_NORM_NONE, norm_mean: torch.Tensor | None = None,
+              norm_scale: torch.Tensor | None = None, norm_eps: float = 0.0) -> LstmDesc:
+    """The descriptor of ``cells``, a list of nn.LSTM layer-0 parameter tuples (weight_ih [4H][d_in], weight_hh [4H][H],
+    bias_ih [4H], bias_hh [4H]), and ``nets``, the MLP after each cell as for mlp_desc.  Shapes and data pointers only;
+    the caller keeps the tensors alive and in place."""
+    if not 1 <= len(cells) <= LSTM_MAX_NETS or len(nets) != len(cells):
+        raise ValueError(f"lstm_desc: {len(cells)} cells and {len(nets)} networks (1..{LSTM_MAX_NETS} of each)")
+    d = LstmDesc()
+    four_h, d.d_in = (int(v) for v in cells[0][0].shape)
+    d.hidden = four_h // 4
+    d.norm_kind, d.norm_eps = int(norm_kind), float(norm_eps)
+    if norm_kind != MLP_NORM_NONE:
+        d.norm_mean, d.norm_scale = norm_mean.data_ptr(), norm_scale.data_ptr()
+    for i, (w_ih, w_hh, b_ih, b_hh) in enumerate(cells):
+        if (w_ih.shape != (four_h, d.d_in) or w_hh.shape != (four_h, d.hidden) or b_ih.shape != (four_h,)
+                or b_hh.shape != (four_h,) or four_h != 4 * d.hidden):
+            raise ValueError(f"lstm_desc: cell {i}: weight_ih {tuple(w_ih.shape)}, weight_hh {tuple(w_hh.shape)}, biases "
+                             f"{tuple(b_ih.shape)}, {tuple(b_hh.shape)}")
+        c = d.cells[i]
+        c.w_ih, c.w_hh, c.b_ih, c.b_hh = w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr()
+    d.mlp = mlp_desc(nets)
+    return d
+
+
+def lstm_packed_bytes(desc: LstmDesc) -> int:
+    lib = learn_library()
+    nbytes = lib.h12learn_lstm_packed_bytes(C.byref(desc))
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_lstm_packed_bytes")
+    return nbytes
+
+
+def lstm_pack(desc: LstmDesc, packed: torch.Tensor):
+    """Re-packs the parameters ``desc`` points to into ``packed`` (one launch on the current stream)."""
+    lib = learn_library()
+    _f32(packed, "packed")
+    if packed.numel() * 4 < lstm_packed_bytes(desc):
+        raise ValueError("lstm_pack: packed is smaller than lstm_packed_bytes(desc)")
+    _check(lib, lib.h12learn_lstm_pack(C.byref(desc), packed.data_ptr(), _stream(packed.device)), "h12learn_lstm_pack")
+
+
+def lstm_step(desc: LstmDesc, packed: torch.Tensor, x: torch.Tensor, states, reset: torch.Tensor | None = None,
+              out_states=None, out=None) -> tuple:
+    """One launch: every network of ``desc`` steps once on ``x`` [n][d_in].  ``states``: per network (h, c), [n][H] each,
+    updated IN PLACE unless ``out_states`` (the same layout) is given.  ``reset``: None, or n uint8 / bool entries; a
+    non-zero entry makes that row read h = c = 0.  Returns the networks' outputs ([n][d_out] each)."""
+    lib = learn_library()
+    _f32(packed, "packed"), _f32(x, "x")
+    nn_ = desc.mlp.n_nets
+    if x.dim() != 2 or x.shape[1] != desc.d_in or x.shape[0] < 1:
+        raise ValueError(f"lstm_step: x {tuple(x.shape)} is not (n >= 1, {desc.d_in})")
+    n = x.shape[0]
+    if out_states is None:
+        out_states = states
+    if len(states) != nn_ or len(out_states) != nn_:
+        raise ValueError(f"lstm_step: {len(states)} states for {nn_} networks")
+    for i, pair in enumerate(list(states) + list(out_states)):
+        for t in pair:
+            if _f32(t, f"states[{i % nn_}]").shape != (n, desc.hidden):
+                raise ValueError(f"lstm_step: every state tensor must be ({n}, {desc.hidden}), got {tuple(t.shape)}")
+    widths = [desc.mlp.nets[i].dims[desc.mlp.nets[i].n_layers] for i in range(nn_)]
+    if out is None:
+        out = tuple(torch.empty((n, w), dtype=torch.float32, device=x.device) for w in widths)
+    for i, (y, w) in enumerate(zip(out, widths)):
+        if _f32(y, f"out[{i}]").shape != (n, w):
+            raise ValueError(f"lstm_step: out[{i}] must be ({n}, {w})")
+    io = LstmIo()
+    io.x, io.n = x.data_ptr(), n
+    if reset is not None:
+        if not (reset.is_cuda and reset.dtype in (torch.uint8, torch.bool) and reset.is_contiguous()
+                and reset.numel() == n):
+            raise ValueError(f"lstm_step: reset must be a contiguous uint8 or bool CUDA tensor of {n} entries")
+        io.reset = reset.data_ptr()
+    for i in range(nn_):
+        io.h_in[i], io.c_in[i] = states[i][0].data_ptr(), states[i][1].data_ptr()
+        io.h_out[i], io.c_out[i] = out_states[i][0].data_ptr(), out_states[i][1].data_ptr()
+        io.y[i] = out[i].data_ptr()
+    _check(lib, lib.h12learn_lstm_step(C.byref(desc), packed.data_ptr(), C.byref(io), _stream(x.device)),
+           "h12learn_lstm_step")
+    return tuple(out)
 
 
 # ---- fused loss heads (csrc/h12_ppo_head.hip): what ppo_head and cleanrl_head check and allocate alike

@@ -97,10 +97,44 @@ class _ExportedPolicy(nn.Module):
         return self.actor(self.normalizer(x))
 
 
+class _ExportedRecurrentPolicy(nn.Module):
+    """IsaacLab's exporter for a recurrent policy (LSTM): a copy of memory_a.rnn, its state for ONE robot in the
+    buffers hidden_state / cell_state (layers, 1, H); forward normalises, steps the rnn, writes the buffers back and
+    runs the actor; reset() zeroes them."""
+
+    def __init__(self, policy, normalizer: nn.Module | None):
+        super().__init__()
+        from .ppo import plain_linear
+
+        self.actor = plain_linear(policy.actor).cpu().eval()
+        self.normalizer = copy.deepcopy(normalizer).cpu().eval() if normalizer is not None else nn.Identity()
+        self.rnn = copy.deepcopy(policy.memory_a.rnn).cpu().eval()
+        if not isinstance(self.rnn, nn.LSTM):
+            raise NotImplementedError(f"recurrent export is implemented for nn.LSTM, not {type(self.rnn).__name__}")
+        self.register_buffer("hidden_state", torch.zeros(self.rnn.num_layers, 1, self.rnn.hidden_size))
+        self.register_buffer("cell_state", torch.zeros(self.rnn.num_layers, 1, self.rnn.hidden_size))
+
+    def forward(self, x):
+        x = self.normalizer(x)
+        x, (h, c) = self.rnn(x.unsqueeze(0), (self.hidden_state, self.cell_state))
+        self.hidden_state[:] = h
+        self.cell_state[:] = c
+        return self.actor(x.squeeze(0))
+
+    @torch.jit.export
+    def reset(self):
+        self.hidden_state[:] = 0.0
+        self.cell_state[:] = 0.0
+
+
 def export_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.pt") -> str:
-    """TorchScript of actor(normalizer(obs)) (play.py:102-108)."""
+    """TorchScript of actor(normalizer(obs)) (play.py:102-108); of a recurrent policy: actor(rnn(normalizer(obs)))
+    with the memory's state in the module's buffers and an exported reset()."""
     os.makedirs(path, exist_ok=True)
-    m = torch.jit.script(_ExportedPolicy(policy.actor, normalizer))
+    if getattr(policy, "is_recurrent", False):
+        m = torch.jit.script(_ExportedRecurrentPolicy(policy, normalizer))
+    else:
+        m = torch.jit.script(_ExportedPolicy(policy.actor, normalizer))
     out = os.path.join(path, filename)
     m.save(out)
     return out
@@ -108,6 +142,9 @@ def export_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.
 
 def export_policy_as_onnx(policy, normalizer, path: str, filename: str = "policy.onnx", verbose: bool = False) -> str:
     """ONNX of actor(normalizer(obs)), input "obs" (1, num_obs), output "actions" (play.py:109-114)."""
+    if getattr(policy, "is_recurrent", False):
+        raise NotImplementedError("ONNX export of a recurrent policy is not implemented (the state would be extra "
+                                  "inputs and outputs of the graph); export_policy_as_jit writes policy.pt")
     try:
         import onnx  # noqa: F401  (torch's exporter serialises through it)
     except ImportError as e:

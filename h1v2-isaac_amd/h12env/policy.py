@@ -52,9 +52,6 @@ def _linears(net: nn.Module, index: int) -> list[nn.Linear]:
 
 class FusedMLP:
     def __init__(self, nets, normalizer: nn.Module | None = None):
-        from .cleanrl import RunningMeanStd
-        from .ppo import EmpiricalNormalization
-
         self.nets = list(nets)
         if not 1 <= len(self.nets) <= _learn.MLP_MAX_NETS:
             raise ValueError(f"FusedMLP: {len(self.nets)} networks (1..{_learn.MLP_MAX_NETS})")
@@ -69,20 +66,7 @@ class FusedMLP:
             for lin in layers:
                 if max(lin.in_features, lin.out_features) > max_width or lin.weight.dtype != torch.float32:
                     raise ValueError(f"FusedMLP: network {i}: {lin} is wider than {max_width} or not float32")
-        if isinstance(normalizer, nn.Identity):
-            normalizer = None
-        self.normalizer = normalizer
-        if normalizer is None:
-            self._norm = (_learn.MLP_NORM_NONE, None, None, 0.0)
-        elif isinstance(normalizer, RunningMeanStd):
-            self._norm = (_learn.MLP_NORM_VAR, normalizer.running_mean, normalizer.running_var, normalizer.epsilon)
-        elif isinstance(normalizer, EmpiricalNormalization):
-            self._norm = (_learn.MLP_NORM_STD, normalizer._mean, normalizer._std, normalizer.eps)
-        else:
-            raise ValueError(f"FusedMLP: normalizer {type(normalizer).__name__} is neither cleanrl.RunningMeanStd nor "
-                             "ppo.EmpiricalNormalization")
-        if normalizer is not None and self._norm[1].numel() != d_in:
-            raise ValueError(f"FusedMLP: normalizer of {self._norm[1].numel()} columns on {d_in} inputs")
+        self.normalizer, self._norm = _norm_of(normalizer, d_in, "FusedMLP")
         self.d_in = d_in
         self._desc = None
         self._packed = None
@@ -183,6 +167,221 @@ class FusedMLP:
         for p in actor.parameters():
             p.requires_grad_(False)
         return cls([actor], norm.to(device) if norm is not None else None)
+
+
+def _norm_of(normalizer, d_in: int, who: str):
+    """(normalizer or None, (kind, mean, scale, eps)) as FusedMLP reads a normaliser."""
+    from .cleanrl import RunningMeanStd
+    from .ppo import EmpiricalNormalization
+
+    if normalizer is None or isinstance(normalizer, nn.Identity):
+        return None, (_learn.MLP_NORM_NONE, None, None, 0.0)
+    if isinstance(normalizer, RunningMeanStd):
+        norm = (_learn.MLP_NORM_VAR, normalizer.running_mean, normalizer.running_var, normalizer.epsilon)
+    elif isinstance(normalizer, EmpiricalNormalization):
+        norm = (_learn.MLP_NORM_STD, normalizer._mean, normalizer._std, normalizer.eps)
+    else:
+        raise ValueError(f"{who}: normalizer {type(normalizer).__name__} is neither cleanrl.RunningMeanStd nor "
+                         "ppo.EmpiricalNormalization")
+    if norm[1].numel() != d_in:
+        raise ValueError(f"{who}: normalizer of {norm[1].numel()} columns on {d_in} inputs")
+    return normalizer, norm
+
+
+def lstm_step_limit(rnn: nn.Module) -> str | None:
+    """Why h12learn_lstm_step cannot run ``rnn`` (None: it can): one-layer fp32 nn.LSTM of at most lstm_max_hidden()."""
+    if not isinstance(rnn, nn.LSTM):
+        return f"{type(rnn).__name__}: the fused step is LSTM only"
+    if rnn.num_layers != 1 or rnn.bidirectional or rnn.proj_size != 0 or not rnn.bias:
+        return f"num_layers = {rnn.num_layers}: the fused step is one unidirectional layer with biases, no projection"
+    if rnn.hidden_size > _learn.lstm_max_hidden():
+        return f"hidden size {rnn.hidden_size}: the fused step supports at most {_learn.lstm_max_hidden()}"
+    if rnn.input_size > _learn.mlp_max_width() or rnn.weight_ih_l0.dtype != torch.float32:
+        return f"input size {rnn.input_size} is wider than {_learn.mlp_max_width()} or the weights are not float32"
+    return None
+
+
+class FusedLSTMStep:
+    """One step of up to two (nn.LSTM, Linear/ELU nn.Sequential) pairs over one shared input as ONE HIP launch
+    (h12learn_lstm_step, csrc/h12_policy_rnn.hip).  ``step(x, states)`` with ``states`` a list of (h, c) [n][H] tensors
+    per pair, updated in place; returns the MLPs' outputs.  ``refresh()`` / ``repack=True`` re-pack the weights (one
+    launch, capturable) as for FusedMLP; the first call at more than 64 KiB of LDS must be made outside a capture."""
+
+    def __init__(self, pairs, normalizer: nn.Module | None = None):
+        self.pairs = list(pairs)
+        if not 1 <= len(self.pairs) <= _learn.LSTM_MAX_NETS:
+            raise ValueError(f"FusedLSTMStep: {len(self.pairs)} networks (1..{_learn.LSTM_MAX_NETS})")
+        for rnn, _ in self.pairs:
+            why = lstm_step_limit(rnn)
+            if why:
+                raise ValueError(f"FusedLSTMStep: {why}")
+        r0 = self.pairs[0][0]
+        self.d_in, self.hidden = r0.input_size, r0.hidden_size
+        self._layers = [_linears(net, i) for i, (_, net) in enumerate(self.pairs)]
+        for i, ((rnn, _), layers) in enumerate(zip(self.pairs, self._layers)):
+            if (rnn.input_size, rnn.hidden_size) != (self.d_in, self.hidden) or layers[0].in_features != self.hidden:
+                raise ValueError(f"FusedLSTMStep: network {i} is {rnn.input_size} -> {rnn.hidden_size} -> "
+                                 f"{layers[0].in_features}, network 0 is {self.d_in} -> {self.hidden}")
+            if len(layers) > _learn.MLP_MAX_LAYERS or any(
+                    max(lin.in_features, lin.out_features) > _learn.mlp_max_width() for lin in layers):
+                raise ValueError(f"FusedLSTMStep: network {i} has more than {_learn.MLP_MAX_LAYERS} layers or one wider "
+                                 f"than {_learn.mlp_max_width()}")
+        self.normalizer, self._norm = _norm_of(normalizer, self.d_in, "FusedLSTMStep")
+        self._desc = self._packed = self._keep = self._ptrs = None
+
+    def _describe(self):
+        kind, mean, scale, eps = self._norm
+        if kind == _learn.MLP_NORM_STD:  # EmpiricalNormalization.update rebinds _std
+            mean, scale = self.normalizer._mean, self.normalizer._std
+        cells = [tuple(p.detach() for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0))
+                 for rnn, _ in self.pairs]
+        nets = [[(lin.weight.detach(), lin.bias.detach()) for lin in layers] for layers in self._layers]
+        tensors = [t for c in cells for t in c] + [t for net in nets for pair in net for t in pair]
+        nm = ns = None
+        if kind != _learn.MLP_NORM_NONE:
+            nm, ns = mean.detach().reshape(-1), scale.detach().reshape(-1)
+            tensors += [nm, ns]
+        ptrs = tuple(t.data_ptr() for t in tensors)
+        if self._desc is not None and ptrs == self._ptrs:
+            return self._desc
+        dev = tensors[0].device
+        for t in tensors:
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("FusedLSTMStep: every parameter and statistic must be a contiguous float32 tensor on "
+                                 "one CUDA device")
+        self._desc = _learn.lstm_desc(cells, nets, kind, nm, ns, eps)
+        self._keep, self._ptrs = tensors, ptrs
+        nfloat = _learn.lstm_packed_bytes(self._desc) // 4
+        if self._packed is None or self._packed.numel() != nfloat or self._packed.device != dev:
+            self._packed = torch.empty(nfloat, dtype=torch.float32, device=dev)
+        return self._desc
+
+    def refresh(self):
+        _learn.lstm_pack(self._describe(), self._packed)
+        return self
+
+    def __call__(self, x: torch.Tensor, states, repack: bool = False, reset: torch.Tensor | None = None,
+                 out_states=None) -> tuple:
+        before = self._desc
+        desc = self._describe()
+        if repack or desc is not before:
+            _learn.lstm_pack(desc, self._packed)
+        return _learn.lstm_step(desc, self._packed, x.detach().contiguous(), states, reset=reset, out_states=out_states)
+
+
+class RecurrentPolicy:
+    """The stateful inference policy of a recurrent actor: ``obs [n][d_in] -> actions``, keeping its own (n, H) memory.
+
+        p = RecurrentPolicy(policy.memory_a.rnn, policy.actor, obs_normalizer, fused=True)
+        actions = p(obs);  p.reset(dones)          # zero the rows of finished episodes;  p.reset(): all of them
+
+    ``fused=True`` on CUDA tensors: one h12learn_lstm_step launch per call, in place on the state; it raises ValueError
+    when the kernel cannot run the memory (GRU, more than one layer, hidden size above lstm_max_hidden()), naming the
+    limit.  Otherwise, and on CPU tensors, the torch modules run.  The weights are packed at construction; call
+    ``refresh()`` after they change.  No autograd."""
+
+    def __init__(self, rnn: nn.Module, mlp: nn.Module, normalizer: nn.Module | None = None, fused: bool = False):
+        self.rnn, self.mlp = rnn, mlp
+        self.normalizer = None if isinstance(normalizer, nn.Identity) else normalizer
+        self.fused = bool(fused)
+        self._step = None
+        if self.fused:
+            why = lstm_step_limit(rnn)
+            if why:
+                raise ValueError(f"RecurrentPolicy(fused=True): {why}; the torch path (fused=False) runs it")
+            self._step = FusedLSTMStep([(rnn, mlp)], self.normalizer)
+        self.state = None  # LSTM: (h, c), GRU: (h,); [layers][n][H] each
+
+    def refresh(self):
+        if self._step is not None and self._step._packed is not None:
+            self._step.refresh()
+        return self
+
+    def _ensure_state(self, n: int, device):
+        if self.state is None or self.state[0].shape[1] != n or self.state[0].device != device:
+            k = 2 if isinstance(self.rnn, nn.LSTM) else 1
+            with torch.inference_mode(False):
+                self.state = tuple(torch.zeros(self.rnn.num_layers, n, self.rnn.hidden_size, device=device)
+                                   for _ in range(k))
+
+    def reset(self, dones=None):
+        if self.state is None:
+            return
+        for s in self.state:
+            if dones is None:
+                s.zero_()
+            else:
+                s[:, dones.to(s.device).reshape(-1) != 0] = 0.0
+
+    @torch.no_grad()
+    def __call__(self, obs: torch.Tensor) -> torch.Tensor:
+        self._ensure_state(obs.shape[0], obs.device)
+        if self._step is not None and obs.is_cuda:
+            (y,) = self._step(obs.float(), [(self.state[0][0], self.state[1][0])])
+            return y
+        x = obs if self.normalizer is None else self.normalizer(obs)
+        hx = self.state if len(self.state) > 1 else self.state[0]
+        out, new = self.rnn(x.unsqueeze(0), hx)
+        for dst, src in zip(self.state, new if len(self.state) > 1 else (new,)):
+            dst.copy_(src)
+        return self.mlp(out.squeeze(0))
+
+    @classmethod
+    def from_exported(cls, jit_module, num_envs: int, device=None, fused: bool = False) -> "RecurrentPolicy":
+        """The memory, actor and normaliser of a recurrent ``policy.pt`` (h12env.export: ``rnn.*``, ``actor.<k>.*``,
+        ``normalizer.*``), with a state of ``num_envs`` rows: the export's own (1, 1, H) buffers serve one robot."""
+        from .ppo import EmpiricalNormalization
+
+        sd = jit_module.state_dict()
+        if "rnn.weight_ih_l0" not in sd:
+            raise ValueError("RecurrentPolicy.from_exported: no rnn.weight_ih_l0 in the module's state_dict")
+        w_ih, w_hh = sd["rnn.weight_ih_l0"], sd["rnn.weight_hh_l0"]
+        hidden = w_hh.shape[1]
+        gates = w_ih.shape[0] // hidden
+        if gates not in (3, 4):
+            raise ValueError(f"RecurrentPolicy.from_exported: {gates} gates per unit (LSTM has 4, GRU 3)")
+        layers = len([k for k in sd if k.startswith("rnn.weight_ih_l")])
+        rnn = (nn.LSTM if gates == 4 else nn.GRU)(w_ih.shape[1], hidden, num_layers=layers)
+        rnn.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("rnn.")})
+        kinds = [getattr(m, "original_name", type(m).__name__) for m in jit_module.actor.children()]
+        mods: list[nn.Module] = []
+        for k, name in enumerate(kinds):
+            if name == "Linear":
+                w = sd[f"actor.{k}.weight"]
+                lin = nn.Linear(w.shape[1], w.shape[0])
+                lin.load_state_dict({"weight": w, "bias": sd[f"actor.{k}.bias"]})
+                mods.append(lin)
+            elif name == "ELU":
+                mods.append(nn.ELU())
+            else:
+                raise ValueError(f"RecurrentPolicy.from_exported: actor.{k} is {name}; only Linear and ELU are supported")
+        norm = None
+        if "normalizer._mean" in sd:
+            norm = EmpiricalNormalization([sd["normalizer._mean"].shape[-1]],
+                                          eps=float(getattr(jit_module.normalizer, "eps", 1e-2)))
+            norm.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("normalizer.")})
+            norm.eval()
+        if device is None:
+            device = w_ih.device
+        actor = nn.Sequential(*mods).to(device).eval()
+        rnn = rnn.to(device).eval()
+        for p in list(actor.parameters()) + list(rnn.parameters()):
+            p.requires_grad_(False)
+        p = cls(rnn, actor, norm.to(device) if norm is not None else None, fused=fused)
+        p._ensure_state(num_envs, torch.device(device))
+        return p
+
+
+def deploy_policy(jit_module, num_envs: int, device, fused: bool = False):
+    """The callable obs [num_envs][d] -> actions of an exported ``policy.pt`` for the batched deploy loops (sim2sim.py,
+    eval_policy.py).  A recurrent export (it has an ``rnn``) keeps (1, 1, H) state buffers that cannot serve num_envs
+    robots: it is rebuilt as a RecurrentPolicy with a state of num_envs rows.  ``fused``: the HIP kernels."""
+    if hasattr(jit_module, "rnn"):
+        return RecurrentPolicy.from_exported(jit_module, num_envs, device=device, fused=fused)
+    if fused:
+        f = FusedMLP.from_exported(jit_module, device=device)
+        return lambda x: f(x)[0]
+    return jit_module
 
 
 def learner_fused_enabled() -> bool:

@@ -32,6 +32,7 @@ import torch.nn as nn
 from torch.distributions import Normal
 
 from . import distributed as D
+from .recurrent import Memory, split_and_pad_trajectories, state_tensors
 
 
 # ---------------------------------------------------------------------------------------------- modules
@@ -186,6 +187,45 @@ class ActorCritic(nn.Module):
         pass
 
 
+class ActorCriticRecurrent(ActorCritic):
+    """rsl_rl's ActorCriticRecurrent: ``memory_a`` reads the actor observation, ``memory_c`` the critic observation,
+    and the actor and critic MLPs read the memories' hidden state.  Collection steps the memories (``masks is None``);
+    the update runs them over padded trajectories from ``hidden_states`` (h12env.recurrent.Memory).  State-dict keys are
+    rsl_rl's (memory_a.rnn.*, memory_c.rnn.*, actor.N.*, critic.N.*, std / log_std)."""
+
+    is_recurrent = True
+
+    def __init__(self, num_actor_obs: int, num_critic_obs: int, num_actions: int, actor_hidden_dims=(256, 256, 256),
+                 critic_hidden_dims=(256, 256, 256), activation="elu", rnn_type="lstm", rnn_hidden_dim=256,
+                 rnn_num_layers=1, init_noise_std=1.0, noise_std_type="scalar", **kwargs):
+        if "rnn_hidden_size" in kwargs:  # the spelling of rsl_rl before 2.3
+            rnn_hidden_dim = kwargs.pop("rnn_hidden_size")
+        super().__init__(rnn_hidden_dim, rnn_hidden_dim, num_actions, actor_hidden_dims=actor_hidden_dims,
+                         critic_hidden_dims=critic_hidden_dims, activation=activation, init_noise_std=init_noise_std,
+                         noise_std_type=noise_std_type)
+        self.memory_a = Memory(num_actor_obs, type=rnn_type, num_layers=rnn_num_layers, hidden_size=rnn_hidden_dim)
+        self.memory_c = Memory(num_critic_obs, type=rnn_type, num_layers=rnn_num_layers, hidden_size=rnn_hidden_dim)
+
+    def enable_fused_learner(self):
+        raise ValueError("a recurrent policy's update runs through the library LSTM")
+
+    def reset(self, dones=None):
+        self.memory_a.reset(dones)
+        self.memory_c.reset(dones)
+
+    def act(self, obs, masks=None, hidden_states=None):
+        return super().act(self.memory_a(obs, masks, hidden_states).squeeze(0))
+
+    def act_inference(self, obs):
+        return super().act_inference(self.memory_a(obs).squeeze(0))
+
+    def evaluate(self, critic_obs, masks=None, hidden_states=None):
+        return super().evaluate(self.memory_c(critic_obs, masks, hidden_states).squeeze(0))
+
+    def get_hidden_states(self):
+        return self.memory_a.hidden_states, self.memory_c.hidden_states
+
+
 class EmpiricalNormalization(nn.Module):
     """Running mean / variance normaliser (rsl_rl EmpiricalNormalization); statistics frozen in eval."""
 
@@ -242,7 +282,11 @@ class EmpiricalNormalization(nn.Module):
 
 # ---------------------------------------------------------------------------------------------- storage
 class RolloutStorage:
-    """(T, N, ...) device tensors of one PPO iteration (rsl_rl RolloutStorage, feed-forward case)."""
+    """(T, N, ...) device tensors of one PPO iteration (rsl_rl RolloutStorage).
+
+    Recurrent policies: ``save_start_states`` takes the memories' states as they were BEFORE the act / evaluate of
+    t = 0 and those only (rsl_rl keeps every step's).  PPO.process_env_step zeroes the state right after a done, so every
+    trajectory that starts later than t = 0 starts from zeros, and recurrent_mini_batch_generator needs no more."""
 
     def __init__(self, num_envs, num_steps, obs_dim, critic_obs_dim, num_actions, device):
         T, N = num_steps, num_envs
@@ -289,6 +333,62 @@ class RolloutStorage:
 
     def clear(self):
         self.step = 0
+
+    def save_start_states(self, hidden_states):
+        """Copies of (actor memory state, critic memory state) at t = 0; a memory that has not stepped yet (None) is
+        recorded as None and read as zeros.  The copies are ordinary tensors also when collection runs in inference
+        mode: the update's LSTM saves them for its backward."""
+        with torch.inference_mode(False):
+            self.start_states = [None if h is None else tuple(torch.empty(x.shape, dtype=x.dtype, device=self.device)
+                                                              for x in state_tensors(h)) for h in hidden_states]
+        for dst, h in zip(self.start_states, hidden_states):
+            if dst is not None:
+                for d, x in zip(dst, state_tensors(h)):
+                    d.copy_(x)
+
+    def recurrent_mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 8, memories=None):
+        """rsl_rl's recurrent generator.  Minibatches split over ENVS (mini_batch_size = num_envs // num_mini_batches),
+        in env order.  Yields, per epoch and minibatch, a dict: the padded observation trajectories of those envs
+        ("observations", "critic_observations": [T, n_traj, ...]) with their "masks" [T, n_traj], the trajectories'
+        start states ("hidden_a", "hidden_c": per state tensor [layers, n_traj, H]; the stored t = 0 state for an env's
+        first trajectory, zeros for the others), and the [T, envs, ...] slices of actions, values, returns,
+        advantages, actions_log_prob, mu and sigma.  ``memories``: the (actor, critic) Memory modules, read for the state
+        shapes when a memory had not stepped before t = 0."""
+        t = self.t
+        T, N = self.num_steps, self.num_envs
+        obs_traj, masks = split_and_pad_trajectories(t["observations"], t["dones"])
+        cobs_traj = (split_and_pad_trajectories(t["privileged_observations"], t["dones"])[0] if "privileged_observations" in t
+                     else obs_traj)
+        starts = torch.zeros(T, N, dtype=torch.bool, device=self.device)  # a trajectory starts at (t, env)
+        starts[0] = True
+        starts[1:] = t["dones"][:-1, :, 0] != 0
+        per_env = starts.sum(0)
+        first = torch.cat([per_env.new_zeros(1), per_env.cumsum(0)]).tolist()  # env e's first trajectory
+        mb = N // num_mini_batches
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                e0, e1 = i * mb, (i + 1) * mb
+                k0, k1 = first[e0], first[e1]
+                at = torch.tensor(first[e0:e1], device=self.device) - k0
+                hidden = []
+                for which in (0, 1):
+                    saved = self.start_states[which] if getattr(self, "start_states", None) else None
+                    if saved is None:
+                        rnn = memories[which].rnn
+                        n_state = 2 if isinstance(rnn, nn.LSTM) else 1
+                        saved = tuple(torch.zeros(rnn.num_layers, N, rnn.hidden_size, device=self.device)
+                                      for _ in range(n_state))
+                    states = []
+                    for s0 in saved:
+                        h = torch.zeros(s0.shape[0], k1 - k0, s0.shape[2], device=self.device, dtype=s0.dtype)
+                        h[:, at] = s0[:, e0:e1]
+                        states.append(h)
+                    hidden.append(tuple(states) if len(states) > 1 else states[0])
+                out = {"observations": obs_traj[:, k0:k1], "critic_observations": cobs_traj[:, k0:k1],
+                       "masks": masks[:, k0:k1], "hidden_a": hidden[0], "hidden_c": hidden[1]}
+                for k in ("actions", "values", "returns", "advantages", "actions_log_prob", "mu", "sigma"):
+                    out[k] = t[k][:, e0:e1]
+                yield out
 
     def compute_returns(self, last_values, gamma, lam, normalize_advantage=True):
         """GAE(gamma, lambda) backwards over the T steps, bootstrapped by last_values."""
@@ -382,6 +482,16 @@ class PPO:
 
             fused_learner = learner_fused_enabled()
         self.fused_learner = bool(fused_learner)
+        self.recurrent = bool(getattr(policy, "is_recurrent", False))
+        if self.recurrent:  # the update of a recurrent policy is the eager library-LSTM path only
+            for name, on in (("fused_learner", fused_learner), ("fused_loss", fused_loss), ("symmetry_cfg", symmetry_cfg),
+                             ("shard.world > 1", self.shard.world > 1)):
+                if name == "fused_loss" and on is None:
+                    from .ppo_head import fused_loss_enabled
+
+                    on = fused_loss_enabled()
+                if on:
+                    raise ValueError(f"{name} is not supported with a recurrent policy ({type(policy).__name__})")
         if self.fused_learner:
             if precision == "bf16":
                 raise ValueError("fused_learner: the fused kernels are exact fp32, precision='bf16' is not supported")
@@ -435,6 +545,10 @@ class PPO:
 
     # ---- collection
     def act(self, obs, critic_obs):
+        if self.recurrent:
+            self._obs_rows = obs.shape[0]
+            if self.storage is not None and self.storage.step == 0:  # the states as they are before this step
+                self.storage.save_start_states(self.policy.get_hidden_states())
         if self._act_graph_ok(obs, critic_obs):
             return self._act_graphed(obs, critic_obs)
         self._obs, self._critic_obs = obs, critic_obs
@@ -452,14 +566,56 @@ class PPO:
 
     # ---- collection as a HIP graph: actor + critic forward, Gaussian sample, log-probability in one launch
     def _act_graph_ok(self, obs, critic_obs) -> bool:
+        # a recurrent policy's collection is captured on the fused step only: it updates the state in place
         return (obs.is_cuda and not torch.is_grad_enabled() and os.environ.get("H12_PPO_GRAPH", "1") != "0"
-                and not getattr(self.policy, "is_recurrent", False))
+                and (not self.recurrent or self._act_fused_ok(obs)))
 
     def _act_fused_ok(self, obs) -> bool:
         from .policy import fused_collection_enabled
 
-        return (fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled()
-                and not getattr(self.policy, "is_recurrent", False))
+        return fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled()
+
+    def _fused_states(self):
+        """The (h, c) [N][H] views of the two memories' states for h12learn_lstm_step, which updates them in place.  A
+        memory that has not stepped gets zeros; the memories keep their storage from here on (Memory.keep_storage), so
+        the torch step of compute_returns and reset(dones) write into the same tensors the captured graph points to."""
+        from .policy import lstm_step_limit
+
+        out = []
+        n = self._obs_rows
+        for mem in (self.policy.memory_a, self.policy.memory_c):
+            why = lstm_step_limit(mem.rnn)
+            if why:
+                raise ValueError(f"H12_POLICY_FUSED=1: {why}; unset it to collect on the torch path")
+            hs = mem.hidden_states
+            if hs is None or any(t.is_inference() for t in hs):
+                with torch.inference_mode(False):
+                    new = tuple(torch.zeros(1, n, mem.rnn.hidden_size, device=self.device) for _ in range(2))
+                if hs is not None:
+                    for d, t in zip(new, hs):
+                        d.copy_(t)
+                hs = mem.hidden_states = new
+            mem.keep_storage = True
+            out.append((hs[0][0], hs[1][0]))
+        return out
+
+    def _act_fused_recurrent(self, obs, cobs):
+        """H12_POLICY_FUSED=1 with a recurrent policy: LSTM cell and MLP of actor and critic from h12learn_lstm_step, one
+        two-network launch when both read the same observation, re-packed in the same body, the memories' states
+        updated in place."""
+        from .policy import FusedLSTMStep
+
+        p = self.policy
+        shared = cobs is obs
+        f = getattr(self, "_fused_rnn", None)
+        if f is None or f[0] != shared:
+            steps = ((FusedLSTMStep([(p.memory_a.rnn, p.actor), (p.memory_c.rnn, p.critic)]),) if shared else
+                     (FusedLSTMStep([(p.memory_a.rnn, p.actor)]), FusedLSTMStep([(p.memory_c.rnn, p.critic)])))
+            f = self._fused_rnn = (shared, steps)
+        sa, sc = self._fused_states()
+        if shared:
+            return f[1][0](obs, [sa, sc], repack=True)
+        return f[1][0](obs, [sa], repack=True)[0], f[1][1](cobs, [sc], repack=True)[0]
 
     def _act_fused(self, obs, cobs):
         """H12_POLICY_FUSED=1: actor mean and critic value from h12learn_mlp_forward, one two-network launch when
@@ -467,6 +623,8 @@ class PPO:
         captured graph): they can never be stale after an update."""
         from .policy import FusedMLP
 
+        if self.recurrent:
+            return self._act_fused_recurrent(obs, cobs)
         shared = cobs is obs
         f = getattr(self, "_fused_mlp", None)
         if f is None or f[0] != shared:
@@ -496,11 +654,14 @@ class PPO:
 
     def _act_graphed(self, obs, critic_obs):
         key = (tuple(obs.shape), tuple(critic_obs.shape), critic_obs is obs, obs.dtype)
+        states = [t for pair in self._fused_states() for t in pair] if self.recurrent else []
+        key += tuple(t.data_ptr() for t in states)
         if getattr(self, "_ga", None) is None or self._ga_key != key:
             # normal (not inference) tensors throughout: the graph's RNG state is updated outside inference mode
             # the warm-up and capture consume exploration-noise draws: the generator state is put back after
             # them, so the replays draw the same noise sequence as the eager path (graph-safe philox offsets)
             rng_state = torch.cuda.get_rng_state(obs.device)
+            kept = [t.clone() for t in states]  # the warm-up steps a recurrent policy's state: put back below
             with torch.inference_mode(False), torch.no_grad():
                 self._ga_obs = torch.zeros(obs.shape, dtype=obs.dtype, device=obs.device)
                 self._ga_cobs = (self._ga_obs if critic_obs is obs else
@@ -515,6 +676,8 @@ class PPO:
                 with torch.cuda.graph(g):
                     self._act_body()
             torch.cuda.set_rng_state(rng_state, obs.device)
+            for t, k in zip(states, kept):
+                t.copy_(k)
             self._ga, self._ga_key = g, key
         self._ga_obs.copy_(obs)
         if critic_obs is not obs:
@@ -588,20 +751,25 @@ class PPO:
                 for g in self.optimizer.param_groups:
                     g["lr"] = self.learning_rate
 
-    def _minibatch(self, b: dict, idx: torch.Tensor, stats: torch.Tensor):
+    def _minibatch(self, b: dict, idx: torch.Tensor | None, stats: torch.Tensor, rec: dict | None = None):
         """One PPO minibatch update (rsl_rl ppo.py update loop body): gather, forward, KL-adaptive learning
         rate, clipped surrogate + clipped value loss, backward, (all-reduce), grad clip, Adam, statistics.
         Host-sync free on the fused path, so it is also the body of the captured HIP graph.
 
         With fused_loss only the observations are gathered here (and the actions where they are mirrored); everything
         from get_actions_log_prob to loss is one PPOHead node, which on a single CUDA rank also applies the adaptive
-        schedule to _lr_t and, without symmetry, adds the statistics."""
+        schedule to _lr_t and, without symmetry, adds the statistics.
+
+        ``rec`` (a recurrent policy; b and idx are then None): one yield of recurrent_mini_batch_generator.  The networks
+        run in batch mode over its padded trajectories; the per-sample tensors are its [T, envs, ...] slices."""
         sym = self.symmetry
         fused = self.fused_loss
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         aug = sym is not None and sym["use_data_augmentation"]
-        n_orig = idx.shape[0]
-        if aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
+        n_orig = 0 if rec is not None else idx.shape[0]
+        if rec is not None:
+            obs, critic_obs, actions = rec["observations"], rec["critic_observations"], rec["actions"]
+        elif aug:  # rows [0, B) the minibatch, rows [B, 2B) its mirror image
             obs, actions = self._augment(b["observations"], b["actions"], idx, "policy")
             critic_obs = (self._augment(b["privileged_observations"], None, idx, "critic")[0]
                           if "privileged_observations" in b else obs)
@@ -609,7 +777,12 @@ class PPO:
             obs = b["observations"][idx]
             critic_obs = b["privileged_observations"][idx] if "privileged_observations" in b else obs
             actions = b["actions"] if fused else b["actions"][idx]  # the head gathers its rows itself
-        if not fused:
+        if rec is not None:
+            target_values, advantages, returns = rec["values"], rec["advantages"], rec["returns"]
+            old_log_prob, old_mu, old_sigma = rec["actions_log_prob"], rec["mu"], rec["sigma"]
+            if self.normalize_advantage_per_mini_batch:
+                advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-8)
+        elif not fused:
             target_values = b["values"][idx]
             advantages = b["advantages"][idx]
             returns = b["returns"][idx]
@@ -622,8 +795,12 @@ class PPO:
                                                                     (old_log_prob, target_values, advantages, returns))
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
                             enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
-            self.policy.update_distribution(obs)  # rsl_rl calls act(); the sample itself is unused
-            value = self.policy.evaluate(critic_obs).float()
+            if rec is not None:  # batch mode: the library LSTM over the padded trajectories, from their start states
+                self.policy.act(obs, masks=rec["masks"], hidden_states=rec["hidden_a"])
+                value = self.policy.evaluate(critic_obs, masks=rec["masks"], hidden_states=rec["hidden_c"]).float()
+            else:
+                self.policy.update_distribution(obs)  # rsl_rl calls act(); the sample itself is unused
+                value = self.policy.evaluate(critic_obs).float()
         if self.precision == "bf16":  # distribution statistics in fp32
             self.policy.distribution = Normal(self.policy.distribution.mean.float(),
                                               self.policy.distribution.stddev.float())
@@ -750,7 +927,21 @@ class PPO:
         self._graph = g
         self._graph_key = (mb, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in sorted(b.items())))
 
+    def _update_recurrent(self):
+        """The update of a recurrent policy: eager (the number of trajectories changes every iteration, so there is
+        no graph to capture), minibatches over envs from recurrent_mini_batch_generator."""
+        stats = torch.zeros(self._n_stats, device=self.device)
+        n_updates = 0
+        memories = (self.policy.memory_a, self.policy.memory_c)
+        for rec in self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, memories):
+            self._minibatch(None, None, stats, rec=rec)
+            n_updates += 1
+        return stats, n_updates
+
     def update(self):
+        if self.recurrent:
+            stats, n_updates = self._update_recurrent()
+            return self._finish_update(stats, n_updates)
         b = self._batch()
         n_total = b["observations"].shape[0]
         mb = n_total // self.num_mini_batches
@@ -781,6 +972,9 @@ class PPO:
                 else:
                     self._minibatch(b, idx, stats)
                 n_updates += 1
+        return self._finish_update(stats, n_updates)
+
+    def _finish_update(self, stats, n_updates):
         self._update_count += 1
         self.storage.clear()
         if self._lr_t is not None:
@@ -859,8 +1053,11 @@ class OnPolicyRunner:
         num_obs = obs.shape[1]
         critic_obs = extras["observations"].get("critic")
         num_critic_obs = critic_obs.shape[1] if critic_obs is not None else num_obs
-        self.policy_cfg.pop("class_name", None)
-        policy = ActorCritic(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
+        class_name = self.policy_cfg.pop("class_name", None) or "ActorCritic"
+        classes = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent}
+        if class_name not in classes:
+            raise ValueError(f"policy.class_name = {class_name!r}; this runner builds {sorted(classes)}")
+        policy = classes[class_name](num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         self.alg_cfg.pop("class_name", None)
         self.alg_cfg.pop("rnd_cfg", None)
         if self.alg_cfg.get("symmetry_cfg") is not None:  # rsl_rl hands the env to the augmentation function
@@ -1007,8 +1204,12 @@ class OnPolicyRunner:
 
     def load(self, path: str, load_optimizer: bool = True):
         d = torch.load(path, map_location=self.device, weights_only=True)
-        w = d["model_state_dict"].get("critic.0.weight")
-        mine = self.alg.policy.critic[0].weight.shape[1]
+        if self.alg.policy.is_recurrent:  # the critic's memory reads the observation
+            w = d["model_state_dict"].get("memory_c.rnn.weight_ih_l0")
+            mine = self.alg.policy.memory_c.rnn.input_size
+        else:
+            w = d["model_state_dict"].get("critic.0.weight")
+            mine = self.alg.policy.critic[0].weight.shape[1]
         if w is not None and w.shape[1] != mine:
             raise ValueError(f"{path}: the checkpoint's critic reads {w.shape[1]}-wide observations, this env's "
                              f"critic observation is {mine} wide -- the two were built with different "
@@ -1025,10 +1226,26 @@ class OnPolicyRunner:
 
     def get_inference_policy(self, device=None, fused: bool = False):
         """The deterministic policy obs -> action mean.  ``fused=True``: one h12learn_mlp_forward launch (normaliser +
-        actor, h12env.policy.FusedMLP) packed from the parameters as they are now; the default is the torch path."""
+        actor, h12env.policy.FusedMLP) packed from the parameters as they are now; the default is the torch path.
+
+        A recurrent policy's is stateful: it starts from an empty memory, and the caller resets the rows of finished
+        episodes (``policy.reset(dones)``: the returned callable's own ``reset`` with ``fused``, the policy module's
+        otherwise).  ``fused=True``: h12env.policy.RecurrentPolicy on h12learn_lstm_step."""
         self.eval_mode()
         if device is not None:
             self.alg.policy.to(device)
+        if self.alg.policy.is_recurrent:
+            norm = self.obs_normalizer if self.empirical_normalization else None
+            if norm is not None and device is not None:
+                norm.to(device)
+            if fused:
+                from .policy import RecurrentPolicy
+
+                return RecurrentPolicy(self.alg.policy.memory_a.rnn, self.alg.policy.actor, norm, fused=True)
+            self.alg.policy.reset()
+            if norm is not None:
+                return lambda x: self.alg.policy.act_inference(norm(x))
+            return self.alg.policy.act_inference
         if fused:
             from .policy import FusedMLP
 

@@ -80,7 +80,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--log_dir", type=Path, default=None)
     ap.add_argument("--fused", action="store_true",
-                    help="run policy.pt's actor and normaliser as one fused HIP launch (h12env.policy.FusedMLP)")
+                    help="run policy.pt's actor and normaliser (and memory, when recurrent) as one fused HIP launch "
+                         "(h12env.policy.FusedMLP / RecurrentPolicy)")
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="build the env with the privileged critic observation group, as train.py / play.py do with "
                          "this flag (the exported policy is the actor alone: the evaluation itself does not change)")
@@ -98,11 +99,9 @@ def main(argv=None) -> int:
 
     pcfg = yaml.safe_load((args.policy_dir / "env.yaml").read_text())
     policy = torch.jit.load(str(args.policy_dir / "policy.pt"), map_location=args.device).eval()
-    if args.fused:
-        from h12env.policy import FusedMLP
+    from h12env.policy import deploy_policy
 
-        fused = FusedMLP.from_exported(policy, device=args.device)
-        policy = lambda x: fused(x)[0]  # noqa: E731
+    policy = deploy_policy(policy, args.num_envs, args.device, fused=args.fused)  # a recurrent export: batched state
     cfg = mujoco_cfg()
     cfg.scene.num_envs = args.num_envs
     cfg.sim.device = args.device

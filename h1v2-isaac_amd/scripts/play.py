@@ -29,7 +29,8 @@ def main(argv=None) -> int:
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true",
-                    help="run the policy as one fused HIP launch (h12env.policy.FusedMLP) instead of torch modules")
+                    help="run the policy as one fused HIP launch (h12env.policy.FusedMLP, or RecurrentPolicy for a "
+                         "recurrent checkpoint) instead of torch modules")
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="the checkpoint was trained with train.py --privileged_critic (its critic reads the "
                          "privileged observation group)")
@@ -59,6 +60,14 @@ def main(argv=None) -> int:
     root = os.path.abspath(os.path.join("logs", "rsl_rl", args.experiment_name or agent_cfg.experiment_name))
     path = get_checkpoint_path(root, args.load_run, args.checkpoint)
     print(f"[INFO]: Loading model checkpoint from: {path}")
+    # a recurrent checkpoint (train.py --recurrent) says so itself: the memory's type and size are read from it
+    keys = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
+    recurrent = "memory_a.rnn.weight_ih_l0" in keys
+    if recurrent:
+        w_ih, w_hh = keys["memory_a.rnn.weight_ih_l0"], keys["memory_a.rnn.weight_hh_l0"]
+        agent_cfg.policy.class_name = "ActorCriticRecurrent"
+        rnn = {"rnn_type": "lstm" if w_ih.shape[0] == 4 * w_hh.shape[1] else "gru", "rnn_hidden_dim": w_hh.shape[1],
+               "rnn_num_layers": len([k for k in keys if k.startswith("memory_a.rnn.weight_ih_l")])}
     env = gym.make(args.task, cfg=env_cfg, render_mode="rgb_array" if args.video else None)
     if args.video:  # the reference's play.py: one video from step 0 under <run>/videos/play
         vk = {"video_folder": os.path.join(os.path.dirname(path), "videos", "play"),
@@ -66,7 +75,10 @@ def main(argv=None) -> int:
         print("[INFO] Recording videos during training.")
         env = gym.wrappers.RecordVideo(env, **vk)
     env = RslRlVecEnvWrapper(env)
-    runner = OnPolicyRunner(env, agent_cfg.to_dict(), log_dir=None, device=args.device)
+    train_cfg = agent_cfg.to_dict()
+    if recurrent:
+        train_cfg["policy"].update(rnn)
+    runner = OnPolicyRunner(env, train_cfg, log_dir=None, device=args.device)
     runner.load(path)
     policy = runner.get_inference_policy(device=args.device, fused=args.fused)
     out = os.path.join(os.path.dirname(path), "exported")
@@ -74,13 +86,15 @@ def main(argv=None) -> int:
     write_env_yaml(env_cfg, os.path.join(out, "env.yaml"))
     try:
         export_policy_as_onnx(runner.alg.policy, runner.obs_normalizer, out, "policy.onnx")
-    except ImportError as e:
+    except (ImportError, NotImplementedError) as e:
         print(f"[INFO]: skipping ONNX export ({e})")
     print(f"[INFO]: exported to {out}")
     obs, _ = env.get_observations()
     with torch.inference_mode():
         for timestep in range(1, args.steps + 1):
-            obs, _, _, _ = env.step(policy(obs))
+            obs, _, dones, _ = env.step(policy(obs))
+            if recurrent:  # forget the episodes that ended
+                (policy if args.fused else runner.alg.policy).reset(dones)
             if args.video and timestep == args.video_length:  # exit the play loop after recording one video
                 break
     env.close()

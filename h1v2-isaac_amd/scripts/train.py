@@ -55,6 +55,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="asymmetric actor-critic: the env also returns the noise-free privileged observation group "
                          "\"critic\" (env.observations.critic = CriticObsCfg(), h12env.priv) and the critic reads it")
+    ap.add_argument("--recurrent", action="store_true", default=False,
+                    help="train rsl_rl's ActorCriticRecurrent (an LSTM memory in front of the actor and critic MLPs, whose "
+                         "hidden dims stay the task's); agent.policy.class_name=ActorCriticRecurrent works too, and with "
+                         "this flag agent.policy.rnn_type / rnn_hidden_dim / rnn_num_layers can be overridden")
     ap.add_argument("--fused_learner", action="store_true", default=False,
                     help="the PPO update's actor and critic on the fused HIP forward / backward "
                          "(h12env.policy.TrainableFusedMLP; agent.algorithm.fused_learner=true works too)")
@@ -63,6 +67,18 @@ def build_parser() -> argparse.ArgumentParser:
                          "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
     AppLauncher.add_app_launcher_args(ap)
     return ap
+
+
+def make_recurrent(agent_cfg):
+    """--recurrent: the task's policy cfg as an RslRlPpoActorCriticRecurrentCfg, its other fields kept."""
+    import dataclasses
+
+    from isaaclab_rl.rsl_rl import RslRlPpoActorCriticRecurrentCfg
+
+    if not isinstance(agent_cfg.policy, RslRlPpoActorCriticRecurrentCfg):
+        kept = {f.name: getattr(agent_cfg.policy, f.name) for f in dataclasses.fields(agent_cfg.policy)
+                if f.name != "class_name"}
+        agent_cfg.policy = RslRlPpoActorCriticRecurrentCfg(**kept)
 
 
 def apply_cli(agent_cfg, env_cfg, args):
@@ -134,6 +150,8 @@ def main(argv=None) -> int:
 
     env_cfg = load_cfg_from_registry(args.task, "env_cfg_entry_point")
     agent_cfg = load_cfg_from_registry(args.task, "rsl_rl_cfg_entry_point")
+    if args.recurrent:  # before the overrides, so that agent.policy.rnn_* exist for them
+        make_recurrent(agent_cfg)
     apply_overrides(env_cfg, agent_cfg, hydra_args)
     apply_cli(agent_cfg, env_cfg, args)
     rank = dist.get_rank() if dist.is_initialized() else 0

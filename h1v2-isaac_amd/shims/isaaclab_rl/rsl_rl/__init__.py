@@ -20,6 +20,15 @@ class RslRlPpoActorCriticCfg:
 
 
 @dataclass
+class RslRlPpoActorCriticRecurrentCfg(RslRlPpoActorCriticCfg):
+    """rsl_rl's ActorCriticRecurrent (h12env.ppo.ActorCriticRecurrent): a memory in front of the actor and critic MLPs."""
+    class_name: str = "ActorCriticRecurrent"
+    rnn_type: str = "lstm"
+    rnn_hidden_dim: int = 256
+    rnn_num_layers: int = 1
+
+
+@dataclass
 class RslRlSymmetryCfg:
     """rsl_rl 2.3 symmetry options (isaaclab_rl.rsl_rl.symmetry_cfg.RslRlSymmetryCfg).  data_augmentation_func is
     a callable or a "module:func" string with rsl_rl's signature (obs, actions, env, obs_type) -> (obs, actions);

@@ -1,5 +1,5 @@
 /* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
- * csrc/h12_policy_train.hip, csrc/h12_ppo_head.hip).
+ * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_ppo_head.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
@@ -161,6 +161,76 @@ size_t h12learn_mlp_backward_workspace_bytes(const h12learn_mlp_desc* desc, long
 int h12learn_mlp_backward(const h12learn_mlp_desc* desc, const float* packed_t, const float* dy,
                           const float* const* h, long long n, float* const* dz, float* const* db, float* dx,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fused recurrent policy step (csrc/h12_policy_rnn.hip): input normaliser, one LSTM cell and the Linear/ELU MLP
+ * that reads its hidden state, for up to H12LEARN_LSTM_MAX_NETS networks over one shared input (actor and critic of
+ * rsl_rl's ActorCriticRecurrent when both read the same observation; two calls otherwise), in one launch, in exact
+ * fp32 on the design of h12learn_mlp_forward.  One LSTM layer, hidden size at most h12learn_lstm_max_hidden().
+ *
+ * Per network, with torch.nn.LSTM's layer-0 parameters and gate order (i, f, g, o):
+ *     z  = [x | h] [W_ih | W_hh]^T + (b_ih + b_hh)        the bias is summed once, at pack time
+ *     i, f, o = sigmoid(z_i), sigmoid(z_f), sigmoid(z_o);  g = tanh(z_g)
+ *     c' = f * c + i * g;   h' = o * tanh(c');   y = MLP(h')
+ * sigmoid(z) = 1 / (1 + expf(-z)) with a true division.  A z element is one fmaf chain from the bias over x's columns
+ * (padded to 16), then h's: its order depends on (d_in, hidden) alone, and that of a y element on the MLP's widths, never
+ * on n, on the row's position or on the grid.  The gates stay in LDS. */
+#define H12LEARN_LSTM_MAX_NETS 2
+
+/* One cell's parameters: w_ih [4 hidden][d_in], w_hh [4 hidden][hidden], b_ih and b_hh [4 hidden]; row-major contiguous
+ * fp32 device pointers, read only by h12learn_lstm_pack. */
+typedef struct h12learn_lstm_cell {
+  const float* w_ih;
+  const float* w_hh;
+  const float* b_ih;
+  const float* b_hh;
+} h12learn_lstm_cell;
+
+/* d_in: the width of x; the norm_* fields are the input normaliser of h12learn_mlp_desc, applied to x.  mlp holds the
+ * networks that follow the cells: mlp.n_nets (1..H12LEARN_LSTM_MAX_NETS) is the number of networks of the call,
+ * mlp.d_in == hidden, mlp.norm_kind == H12LEARN_MLP_NORM_NONE; network i reads cell i's h'. */
+typedef struct h12learn_lstm_desc {
+  int d_in;
+  int hidden;
+  int norm_kind;
+  float norm_eps;
+  const float* norm_mean;
+  const float* norm_scale;
+  h12learn_lstm_cell cells[H12LEARN_LSTM_MAX_NETS];
+  h12learn_mlp_desc mlp;
+} h12learn_lstm_desc;
+
+/* The tensors of one step: x [n][d_in], shared by the networks; reset (null, or n bytes): a non-zero byte makes that
+ * row read h = c = 0; per network h_in, c_in, h_out, c_out [n][hidden] and y [n][d_out].  A block owns its 16 rows
+ * completely and reads its rows of h and c before it writes any of them: h_out == h_in and c_out == c_in (in place) is
+ * legal.  No other overlap between an output and an input, or between two networks' states, is. */
+typedef struct h12learn_lstm_io {
+  const float* x;
+  const unsigned char* reset;
+  long long n;
+  const float* h_in[H12LEARN_LSTM_MAX_NETS];
+  const float* c_in[H12LEARN_LSTM_MAX_NETS];
+  float* h_out[H12LEARN_LSTM_MAX_NETS];
+  float* c_out[H12LEARN_LSTM_MAX_NETS];
+  float* y[H12LEARN_LSTM_MAX_NETS];
+} h12learn_lstm_io;
+
+/* The largest supported hidden size (4 * hidden is a layer width of the MLP core). */
+int h12learn_lstm_max_hidden(void);
+
+/* Bytes of the packed weights of desc (shapes only); 0 with h12learn_last_error set when the shapes are invalid. */
+size_t h12learn_lstm_packed_bytes(const h12learn_lstm_desc* desc);
+
+/* One launch: per network the matrix [W_ih | W_hh] in the tiled, zero-padded layout of h12learn_mlp_pack (the K axis
+ * padded per segment: x to 16, then h to 16), the bias b_ih + b_hh, then the network's MLP layers as h12learn_mlp_pack
+ * packs them.  packed: 16-byte aligned, h12learn_lstm_packed_bytes.  Run it after every change of the weights; it may
+ * be captured. */
+int h12learn_lstm_pack(const h12learn_lstm_desc* desc, float* packed, void* stream);
+
+/* One launch, grid (row tiles of 16, networks), from the weights in packed (the parameter pointers of desc are not
+ * read).  The real shape (450 inputs, hidden 256) needs more than 64 KiB of LDS: the first such call of a process
+ * raises the kernel's limit, and fails with H12LEARN_E_HIP ("must be made outside a stream capture (warm up first)")
+ * when its stream is capturing. */
+int h12learn_lstm_step(const h12learn_lstm_desc* desc, const float* packed, const h12learn_lstm_io* io, void* stream);
 
 /* ---- fused PPO loss head (csrc/h12_ppo_head.hip): everything PPO._minibatch (h12env/ppo.py) computes between the
  * networks' outputs and loss.backward(), in two launches: the minibatch gathers of the per-sample tensors, the Gaussian

@@ -319,12 +319,21 @@ class RecurrentPolicy:
         if self._step is not None and obs.is_cuda:
             (y,) = self._step(obs.float(), [(self.state[0][0], self.state[1][0])])
             return y
-        x = obs if self.normalizer is None else self.normalizer(obs)
+        x = obs if self.normalizer is None else self._normalise_torch(obs)
         hx = self.state if len(self.state) > 1 else self.state[0]
         out, new = self.rnn(x.unsqueeze(0), hx)
         for dst, src in zip(self.state, new if len(self.state) > 1 else (new,)):
             dst.copy_(src)
         return self.mlp(out.squeeze(0))
+
+    def _normalise_torch(self, obs):
+        """The normaliser module with its statistics read, never updated, as the kernel reads them:
+        cleanrl.RunningMeanStd has no eval mode and updates on a plain call."""
+        from .cleanrl import RunningMeanStd
+
+        if isinstance(self.normalizer, RunningMeanStd):
+            return self.normalizer(obs, update=False)
+        return self.normalizer(obs)
 
     @classmethod
     def from_exported(cls, jit_module, num_envs: int, device=None, fused: bool = False) -> "RecurrentPolicy":

@@ -30,10 +30,12 @@ import torch.nn as nn
 ROOT = Path(__file__).resolve().parents[1]
 SHIMS = ROOT / "h1v2-isaac_amd" / "shims"
 SCRIPTS = ROOT / "h1v2-isaac_amd" / "scripts"
-if str(SHIMS) not in sys.path:
-    sys.path.insert(0, str(SHIMS))
+for p in (str(SHIMS), str(ROOT / "tests" / "helpers")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 
 from h12env.policy import FusedMLP  # noqa: E402
+from lstm_ref import make_norm  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -72,24 +74,6 @@ def make_nets(d_in, hidden, d_outs, seed):
             if isinstance(m, nn.Linear):
                 nn.init.normal_(m.bias, std=0.3)
     return [n.cuda().requires_grad_(False) for n in nets]
-
-
-def make_norm(kind, d_in, seed):
-    from h12env.cleanrl import RunningMeanStd
-    from h12env.ppo import EmpiricalNormalization
-
-    if kind == "none":
-        return None
-    g = torch.Generator().manual_seed(seed)
-    mean = torch.randn(d_in, generator=g) * 3
-    var = torch.rand(d_in, generator=g) * 4 + 0.05
-    if kind == "var":
-        m = RunningMeanStd(shape=(d_in,))
-        m.running_mean.copy_(mean), m.running_var.copy_(var)
-    else:
-        m = EmpiricalNormalization([d_in]).eval()
-        m._mean.copy_(mean[None]), m._var.copy_(var[None]), m._std.copy_(var.sqrt()[None])
-    return m.cuda()
 
 
 def make_x(n, d_in, norm, seed):

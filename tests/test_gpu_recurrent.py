@@ -2,7 +2,9 @@
 RecurrentPolicy) and the recurrent actor-critic on the real env.  DESIGN.md section 7q.  U = 2^-24.
 
 a  accuracy against an fp64 evaluation of the same fp32 parameters, inputs and state, elementwise inside an a-priori
-   bound propagated in fp64 (``lstm_fp64_with_bound``; the MLP part is the bound of tests/test_gpu_policy.py):
+   bound propagated in fp64 (``lstm_fp64_with_bound`` of tests/helpers/lstm_ref.py, shared with the tests of the
+   normaliser and the shape edges in tests/test_gpu_recurrent_edges.py; the MLP part is the bound of
+   tests/test_gpu_policy.py; e_x = 0 here, no test of this file hands the kernel a normaliser):
        e_z  = e_x |W_ih|^T + e_h |W_hh|^T + (K + 3) U (|x||W_ih|^T + |h||W_hh|^T + |b_ih| + |b_hh|),   K = d_in + H
               (a K + 1 term fmaf chain in any order, and the rounding of b_ih + b_hh at pack time)
        e_s  = e_z / 4 + 8 U s   for s = sigmoid(z)   (1/4-Lipschitz; expf within 2 ulp, one add, one true division)
@@ -19,7 +21,6 @@ f  PPO.act with H12_POLICY_FUSED=1 at 64 envs: graphed == eager bit for bit; ins
 g  training 64 envs x 8 steps with class_name=ActorCriticRecurrent; mean |ratio - 1| of the first minibatch < 1e-3.
 h  play.py --fused and sim2sim.py --fused on a recurrent checkpoint, one subprocess each.
 """
-import copy
 import os
 import subprocess
 import sys
@@ -27,111 +28,24 @@ from pathlib import Path
 
 import pytest
 import torch
-import torch.nn as nn
 
 ROOT = Path(__file__).resolve().parents[1]
 SHIMS = ROOT / "h1v2-isaac_amd" / "shims"
 SCRIPTS = ROOT / "h1v2-isaac_amd" / "scripts"
-if str(SHIMS) not in sys.path:
-    sys.path.insert(0, str(SHIMS))
+for p in (str(SHIMS), str(ROOT / "tests" / "helpers")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 
 from h12env.policy import FusedLSTMStep, RecurrentPolicy  # noqa: E402
+from lstm_ref import clone_states, lstm_fp64_with_bound, make_inputs, make_pairs, torch_cpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 NS = (1, 15, 16, 17, 33)
 REAL = [512, 256, 128]
 # (d_in, H, MLP hidden widths, d_out); the last one needs more than 64 KiB of LDS
 SHAPES = [(1, 16, [], 1), (3, 24, [24], 12), (45, 64, [40, 24], 12), (451, 256, REAL, 12)]
 TASK = "Isaac-Velocity-Flat-H12_12dof-v0"
-
-
-def seq(dims):
-    mods = []
-    for i in range(len(dims) - 1):
-        mods.append(nn.Linear(dims[i], dims[i + 1]))
-        if i + 2 < len(dims):
-            mods.append(nn.ELU())
-    return nn.Sequential(*mods)
-
-
-def make_pairs(shape, n_nets, seed):
-    """n_nets (nn.LSTM, MLP) pairs on the GPU; the second network's output is one column (a critic)."""
-    d_in, H, hidden, d_out = shape
-    torch.manual_seed(seed)
-    pairs = []
-    for i in range(n_nets):
-        rnn, net = nn.LSTM(d_in, H), seq([H] + hidden + [d_out if i == 0 else 1])
-        for p in list(rnn.parameters()) + list(net.parameters()):
-            if p.dim() == 1:
-                nn.init.normal_(p, std=0.3)
-        pairs.append((rnn.cuda().requires_grad_(False), net.cuda().requires_grad_(False)))
-    return pairs
-
-
-def make_inputs(shape, n, n_nets, seed):
-    d_in, H, _, _ = shape
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, d_in, generator=g).cuda()
-    states = [(torch.tanh(torch.randn(n, H, generator=g)).cuda(), (1.5 * torch.randn(n, H, generator=g)).cuda())
-              for _ in range(n_nets)]
-    return x, states
-
-
-def clone_states(states):
-    return [(h.clone(), c.clone()) for h, c in states]
-
-
-@torch.no_grad()
-def lstm_fp64_with_bound(rnn, net, x, h, c, eh=None, ec=None):
-    """(y, h', c') in fp64 from the fp32 parameters of ``rnn`` / ``net`` and the inputs x, h, c, and the a-priori
-    bounds (e_y, e_h', e_c') of an fp32 evaluation whose incoming state is within (eh, ec) of (h, c).  The module
-    docstring has the formulae."""
-    x, h, c = x.double(), h.double(), c.double()
-    eh = torch.zeros_like(h) if eh is None else eh
-    ec = torch.zeros_like(c) if ec is None else ec
-    W_ih, W_hh = rnn.weight_ih_l0.double(), rnn.weight_hh_l0.double()
-    b_ih, b_hh = rnn.bias_ih_l0.double(), rnn.bias_hh_l0.double()
-    H = W_hh.shape[1]
-    K = W_ih.shape[1] + H
-    z = x @ W_ih.T + h @ W_hh.T + b_ih + b_hh
-    ez = eh @ W_hh.abs().T + (K + 3) * U * (x.abs() @ W_ih.abs().T + h.abs() @ W_hh.abs().T + b_ih.abs() + b_hh.abs())
-    zi, zf, zg, zo = z.split(H, dim=1)
-    ei, ef, eg, eo = ez.split(H, dim=1)
-    i, f, g, o = torch.sigmoid(zi), torch.sigmoid(zf), torch.tanh(zg), torch.sigmoid(zo)
-    ei, ef, eo = ei / 4 + 8 * U * i, ef / 4 + 8 * U * f, eo / 4 + 8 * U * o
-    eg = eg + 8 * U * g.abs()
-
-    def prod(a, ea, b, eb):
-        return a.abs() * eb + b.abs() * ea + ea * eb + U * (a * b).abs()
-
-    c2 = f * c + i * g
-    ec2 = prod(f, ef, c, ec) + prod(i, ei, g, eg) + U * c2.abs()
-    t = torch.tanh(c2)
-    et = ec2 + 8 * U * t.abs()
-    h2 = o * t
-    eh2 = prod(o, eo, t, et)
-    y, e = h2, eh2
-    lins = [m for m in net if isinstance(m, nn.Linear)]
-    for k, lin in enumerate(lins):  # the bound of tests/test_gpu_policy.py
-        W, b = lin.weight.double(), lin.bias.double()
-        e = e @ W.abs().T + (W.shape[1] + 2) * U * (y.abs() @ W.abs().T + b.abs())
-        y = y @ W.T + b
-        if k + 1 < len(lins):
-            y = torch.where(y > 0, y, torch.expm1(y))
-            e = e + 4 * U * y.abs()
-    return (y, h2, c2), (e, eh2, ec2)
-
-
-@torch.no_grad()
-def torch_cpu(rnn, net, x, h, c):
-    """torch.nn.LSTM and the MLP on the CPU in fp32."""
-    r = nn.LSTM(rnn.input_size, rnn.hidden_size)
-    r.load_state_dict({k: v.cpu() for k, v in rnn.state_dict().items()})
-    m = copy.deepcopy(net).cpu()
-    out, (h2, c2) = r(x.cpu().unsqueeze(0), (h.cpu().unsqueeze(0), c.cpu().unsqueeze(0)))
-    return m(out[0]), h2[0], c2[0]
 
 
 def fraction(got, ref, bound):

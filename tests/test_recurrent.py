@@ -176,6 +176,52 @@ def test_runner_builds_trains_saves_and_loads_the_recurrent_class(tmp_path):
         OnPolicyRunner(RslRlVecEnvWrapper(ToyEnv()), bad, log_dir=None, device="cpu")
 
 
+def test_runner_trains_the_recurrent_class_with_empirical_normalization(tmp_path):
+    cfg = recurrent_cfg(empirical_normalization=True).to_dict()
+    runner = OnPolicyRunner(RslRlVecEnvWrapper(ToyEnv()), cfg, log_dir=None, device="cpu")
+    norm = runner.obs_normalizer
+    assert runner.empirical_normalization and int(norm.count) == 0 and (norm._std == 1).all()
+    before = {k: v.clone() for k, v in runner.alg.policy.state_dict().items()}
+    runner.learn(2)
+    stats = runner.last_iteration_stats
+    assert all(torch.isfinite(torch.tensor(float(stats[k]))) for k in ("Loss/value_function", "Loss/surrogate"))
+    assert int(norm.count) > 0 and int(runner.critic_obs_normalizer.count) > 0
+    assert not (norm._std == 1).all() and torch.equal(norm._std, torch.sqrt(norm._var))
+    after = runner.alg.policy.state_dict()
+    for k in ("memory_a.rnn.weight_ih_l0", "memory_c.rnn.weight_hh_l0", "actor.0.weight", "critic.2.bias"):
+        assert not torch.equal(before[k], after[k]), k
+    # the deployed policy reads the statistics and leaves them alone; a fresh runner gets them from the checkpoint
+    count, std = int(norm.count), norm._std.clone()
+    path = str(tmp_path / "model.pt")
+    runner.save(path)
+    fresh = OnPolicyRunner(RslRlVecEnvWrapper(ToyEnv()), cfg, log_dir=None, device="cpu")
+    fresh.load(path)
+    obs = torch.randn(3, 64, 6)
+    with torch.no_grad():
+        a, b = runner.get_inference_policy(), fresh.get_inference_policy()
+        assert all(torch.equal(a(o), b(o)) for o in obs)
+    assert int(norm.count) == count == int(fresh.obs_normalizer.count) and torch.equal(norm._std, std)
+    assert torch.equal(fresh.obs_normalizer._std, std)
+
+
+def test_recurrent_policy_reads_a_running_mean_std_without_updating_it():
+    from h12env.cleanrl import RunningMeanStd
+    from h12env.policy import RecurrentPolicy
+
+    torch.manual_seed(2)
+    pol = ActorCriticRecurrent(6, 6, 3, actor_hidden_dims=(8,), critic_hidden_dims=(8,), rnn_hidden_dim=8)
+    norm = RunningMeanStd(shape=(6,))
+    norm.running_mean.copy_(torch.randn(6)), norm.running_var.copy_(torch.rand(6) + 0.5)
+    kept = {k: v.clone() for k, v in norm.state_dict().items()}
+    p = RecurrentPolicy(pol.memory_a.rnn, pol.actor, norm)
+    x = torch.randn(4, 6) * 3
+    with torch.no_grad():
+        y = p(x)
+        out, _ = pol.memory_a.rnn(((x - kept["running_mean"]) / torch.sqrt(kept["running_var"] + norm.epsilon))[None])
+        assert torch.equal(y, pol.actor(out[0]))
+    assert all(torch.equal(v, kept[k]) for k, v in norm.state_dict().items())
+
+
 def test_older_spelling_and_gru():
     p = ActorCriticRecurrent(6, 6, 3, rnn_hidden_size=20, rnn_type="gru", rnn_num_layers=2)
     assert p.memory_a.rnn.hidden_size == 20 and isinstance(p.memory_c.rnn, torch.nn.GRU)

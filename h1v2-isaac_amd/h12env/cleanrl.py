@@ -52,6 +52,9 @@ import torch.nn as nn
 import torch.optim as optim
 from torch.distributions.normal import Normal
 
+from .graphs import TrainingState, capture, graph_enabled
+from .policy import FusedActorCritic, fused_collection_on
+
 
 # ---------------------------------------------------------------------------------------------- cfg
 class _Missing:
@@ -270,29 +273,22 @@ class _Collector:
         self.agent = agent
         self.graphed = graphed
         self._graphs: dict = {}
-        self._fused = None
+        self._fused = FusedActorCritic(agent.actor_mean, agent.critic)
 
     def normalise(self, raw):
         with torch.no_grad():
             return self.agent.obs_rms(raw)
 
     def _act_body(self, obs):
-        from .policy import fused_collection_enabled
-
-        if fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled():
+        if fused_collection_on(obs):
             return self._act_body_fused(obs)
         action, logprob, _, value = self.agent.get_action_and_value(obs)
         return action, logprob, value.flatten()
 
     def _act_body_fused(self, obs):
-        """H12_POLICY_FUSED=1: actor mean and critic value from one two-network h12learn_mlp_forward launch, the
-        weights re-packed in the same body (inside the captured graph, so never stale after an update); the sample
-        and the log-probability are get_action_and_value's."""
-        from .policy import FusedMLP
-
-        if self._fused is None:
-            self._fused = FusedMLP([self.agent.actor_mean, self.agent.critic])
-        mean, value = self._fused(obs, repack=True)
+        """H12_POLICY_FUSED=1: actor mean and critic value from policy.FusedActorCritic (one two-network launch); the
+        sample and the log-probability are get_action_and_value's."""
+        mean, value = self._fused(obs)
         std = torch.exp(self.agent.actor_logstd.expand_as(mean))
         action = mean + std * torch.randn_like(mean)
         return action, Normal(mean, std, validate_args=False).log_prob(action).sum(1), value.flatten()
@@ -325,32 +321,19 @@ class _Collector:
         return out
 
     def _capture(self, kind, x):
-        dev = x.device
         rms = self.agent.obs_rms
-        # warm-up and capture consume noise draws and (normalise_act) update the statistics: both are put back, so
-        # the replays continue exactly where eager collection would
-        rng_state = torch.cuda.get_rng_state(dev)
-        saved = [b.clone() for b in (rms.running_mean, rms.running_var, rms.count)]
+        # the warm-up consumes noise draws and (normalise_act) updates the statistics: both are put back, so the
+        # replays continue exactly where eager collection would
         with torch.no_grad():
             inp = x.detach().clone()
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._body(kind, inp)
-            torch.cuda.current_stream(dev).wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self._body(kind, inp)
-            for b, v in zip((rms.running_mean, rms.running_var, rms.count), saved):
-                b.copy_(v)
-        torch.cuda.set_rng_state(rng_state, dev)
+            g, out = capture(lambda: self._body(kind, inp), x.device,
+                             undo=(rms.running_mean, rms.running_var, rms.count), rng=True)
         return g, inp, out
 
 
 def _graph_enabled(device) -> bool:
     # the graph is built on the HIP normaliser; the torch restatement (H12_CLEANRL_FUSED=0) collects eagerly
-    return device.type == "cuda" and os.environ.get("H12_PPO_GRAPH", "1") != "0" and fused_enabled()
+    return device.type == "cuda" and graph_enabled() and fused_enabled()
 
 
 def _episode_scalars(ep_infos, device) -> dict:
@@ -371,8 +354,8 @@ class _FusedUpdate:
     """The minibatch of ``PPO(fused_loss=True)``: gather the observations, actor and critic forward, ``CleanRLHead``,
     backward, gradient clip, optimiser step.  On CUDA the loss statistics accumulate on the device in ``stats``
     (pg, entropy, v, total, clip fraction) and, graphed, each minibatch size replays a graph of its own, captured at its
-    first use with ``ppo.PPO._capture``'s discipline: warm-up on a side stream, then parameters, optimiser state and
-    statistics put back bit for bit.  On CPU the node evaluates the default path's expressions."""
+    first use (graphs.capture: the warm-up's changes to parameters, optimiser state and statistics are put back bit for
+    bit).  On CPU the node evaluates the default path's expressions."""
 
     def __init__(self, agent, optimizer, cfg, batch_size: int, device, graphed: bool):
         self.agent, self.optimizer, self.cfg, self.device = agent, optimizer, cfg, device
@@ -427,37 +410,11 @@ class _FusedUpdate:
             self.stats[:4] += out[:4]
             self.clipfracs.append(out[4])
 
-    def _snapshot(self):
-        params = list(self.agent.parameters())
-        st = {p: {k: v.detach().clone() for k, v in self.optimizer.state.get(p, {}).items() if torch.is_tensor(v)}
-              for p in params}
-        return [p.detach().clone() for p in params], st, self.stats.clone()
-
-    def _restore(self, snap):
-        params, st, stats = snap
-        with torch.no_grad():
-            for p, v in zip(self.agent.parameters(), params):
-                p.copy_(v)
-                for k, t in self.optimizer.state.get(p, {}).items():
-                    if torch.is_tensor(t):
-                        t.copy_(st[p][k]) if k in st[p] else t.zero_()  # lazily created by the warm-up: initial 0
-            self.stats.copy_(stats)
-
     def _capture(self, mb: int):
-        dev = self.device
-        idx = torch.arange(mb, dtype=torch.long, device=dev)
-        snap = self._snapshot()
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._minibatch(idx)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        self._restore(snap)
-        g = torch.cuda.CUDAGraph()
-        self.optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(g):
-            self._minibatch(idx)
+        idx = torch.arange(mb, dtype=torch.long, device=self.device)
+        state = TrainingState(self.agent.parameters(), self.optimizer, [self.stats])
+        g, _ = capture(lambda: self._minibatch(idx), self.device, undo=[state],
+                       before_capture=lambda: self.optimizer.zero_grad(set_to_none=True))
         return g, idx
 
     def means(self, num_updates: float):

@@ -33,6 +33,11 @@ def fused_collection_enabled() -> bool:
     return os.environ.get("H12_POLICY_FUSED", "0") == "1"
 
 
+def fused_collection_on(obs: torch.Tensor) -> bool:
+    """Fused collection on this tensor, for both trainers: the flag, a CUDA tensor, grad disabled (no autograd)."""
+    return fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled()
+
+
 def _linears(net: nn.Module, index: int) -> list[nn.Linear]:
     if not isinstance(net, nn.Sequential):
         raise ValueError(f"FusedMLP: network {index} is {type(net).__name__}, an nn.Sequential of Linear/ELU is required")
@@ -136,37 +141,43 @@ class FusedMLP:
     def from_exported(cls, jit_module, device=None) -> "FusedMLP":
         """Actor and normaliser of a ``policy.pt`` written by export_policy_as_jit (h12env.export._ExportedPolicy:
         ``actor.<k>.weight/bias`` with ELU between, ``normalizer._mean/_var/_std/count`` when one was exported)."""
-        from .ppo import EmpiricalNormalization
-
         sd = jit_module.state_dict()
-        idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("actor.") and k.endswith(".weight")})
-        if not idx:
-            raise ValueError("FusedMLP.from_exported: no actor.<k>.weight in the module's state_dict")
-        kinds = [getattr(m, "original_name", type(m).__name__) for m in jit_module.actor.children()]
-        mods: list[nn.Module] = []
-        for k, name in enumerate(kinds):
-            if name == "Linear" and k in idx:
-                w = sd[f"actor.{k}.weight"]
-                lin = nn.Linear(w.shape[1], w.shape[0])
-                lin.load_state_dict({"weight": w, "bias": sd[f"actor.{k}.bias"]})
-                mods.append(lin)
-            elif name == "ELU":
-                mods.append(nn.ELU())
-            else:
-                raise ValueError(f"FusedMLP.from_exported: actor.{k} is {name}; only Linear and ELU are supported")
-        actor = nn.Sequential(*mods)
-        norm = None
-        if "normalizer._mean" in sd:
-            norm = EmpiricalNormalization([sd["normalizer._mean"].shape[-1]],
-                                          eps=float(getattr(jit_module.normalizer, "eps", 1e-2)))
-            norm.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("normalizer.")})
-            norm.eval()
+        actor, norm = _exported_actor(jit_module, sd), _exported_normalizer(jit_module, sd)
         if device is None:
             device = next(iter(sd.values())).device
-        actor = actor.to(device).eval()
-        for p in actor.parameters():
-            p.requires_grad_(False)
-        return cls([actor], norm.to(device) if norm is not None else None)
+        return cls([actor.to(device)], norm.to(device) if norm is not None else None)
+
+
+def _exported_actor(jit_module, sd) -> nn.Sequential:
+    """The ``actor`` of an exported policy.pt as a frozen nn.Sequential in eval mode: ``actor.<k>.weight/bias`` with ELU
+    between.  Any other child, or a Linear whose weight the state dict does not hold, is refused."""
+    if not any(k.startswith("actor.") and k.endswith(".weight") for k in sd):
+        raise ValueError("from_exported: no actor.<k>.weight in the module's state_dict")
+    mods: list[nn.Module] = []
+    for k, m in enumerate(jit_module.actor.children()):
+        name = getattr(m, "original_name", type(m).__name__)
+        if name == "Linear" and f"actor.{k}.weight" in sd:
+            w = sd[f"actor.{k}.weight"]
+            lin = nn.Linear(w.shape[1], w.shape[0])
+            lin.load_state_dict({"weight": w, "bias": sd[f"actor.{k}.bias"]})
+            mods.append(lin)
+        elif name == "ELU":
+            mods.append(nn.ELU())
+        else:
+            raise ValueError(f"from_exported: actor.{k} is {name}; only Linear and ELU are supported")
+    return nn.Sequential(*mods).eval().requires_grad_(False)
+
+
+def _exported_normalizer(jit_module, sd):
+    """The ``normalizer`` of an exported policy.pt as an EmpiricalNormalization in eval mode; None without one."""
+    from .ppo import EmpiricalNormalization
+
+    if "normalizer._mean" not in sd:
+        return None
+    norm = EmpiricalNormalization([sd["normalizer._mean"].shape[-1]],
+                                  eps=float(getattr(jit_module.normalizer, "eps", 1e-2)))
+    norm.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("normalizer.")})
+    return norm.eval()
 
 
 def _norm_of(normalizer, d_in: int, who: str):
@@ -269,6 +280,35 @@ class FusedLSTMStep:
         return _learn.lstm_step(desc, self._packed, x.detach().contiguous(), states, reset=reset, out_states=out_states)
 
 
+class FusedActorCritic:
+    """The trainers' collection forward: ``(mean, value) = f(obs, cobs)`` from FusedMLP, or with ``memories`` (the
+    actor's and the critic's nn.LSTM) from FusedLSTMStep, which steps ``states = [(h_a, c_a), (h_c, c_c)]`` in place.
+    One two-network launch when actor and critic read the same observation (``cobs`` is ``obs`` or None), else one
+    launch each.  The weights are re-packed at every call, in the same body and so inside a captured graph: they can
+    never be stale after an update."""
+
+    def __init__(self, actor: nn.Module, critic: nn.Module, memories=None):
+        nets = [actor, critic]
+        self._nets = nets if memories is None else list(zip(memories, nets))
+        self._make = FusedMLP if memories is None else FusedLSTMStep
+        self._shared = self._fused = None
+
+    def __call__(self, obs: torch.Tensor, cobs: torch.Tensor | None = None, states=None) -> tuple:
+        shared = cobs is None or cobs is obs
+        if self._shared != shared:
+            groups = [self._nets] if shared else [self._nets[:1], self._nets[1:]]
+            self._fused = [self._make(g) for g in groups]
+            self._shared = shared
+
+        def run(f, x, st):
+            return f(x, repack=True) if states is None else f(x, st, repack=True)
+
+        if shared:
+            return run(self._fused[0], obs, states)
+        sa, sc = states if states is not None else (None, None)
+        return run(self._fused[0], obs, [sa])[0], run(self._fused[1], cobs, [sc])[0]
+
+
 class RecurrentPolicy:
     """The stateful inference policy of a recurrent actor: ``obs [n][d_in] -> actions``, keeping its own (n, H) memory.
 
@@ -339,8 +379,6 @@ class RecurrentPolicy:
     def from_exported(cls, jit_module, num_envs: int, device=None, fused: bool = False) -> "RecurrentPolicy":
         """The memory, actor and normaliser of a recurrent ``policy.pt`` (h12env.export: ``rnn.*``, ``actor.<k>.*``,
         ``normalizer.*``), with a state of ``num_envs`` rows: the export's own (1, 1, H) buffers serve one robot."""
-        from .ppo import EmpiricalNormalization
-
         sd = jit_module.state_dict()
         if "rnn.weight_ih_l0" not in sd:
             raise ValueError("RecurrentPolicy.from_exported: no rnn.weight_ih_l0 in the module's state_dict")
@@ -352,31 +390,11 @@ class RecurrentPolicy:
         layers = len([k for k in sd if k.startswith("rnn.weight_ih_l")])
         rnn = (nn.LSTM if gates == 4 else nn.GRU)(w_ih.shape[1], hidden, num_layers=layers)
         rnn.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("rnn.")})
-        kinds = [getattr(m, "original_name", type(m).__name__) for m in jit_module.actor.children()]
-        mods: list[nn.Module] = []
-        for k, name in enumerate(kinds):
-            if name == "Linear":
-                w = sd[f"actor.{k}.weight"]
-                lin = nn.Linear(w.shape[1], w.shape[0])
-                lin.load_state_dict({"weight": w, "bias": sd[f"actor.{k}.bias"]})
-                mods.append(lin)
-            elif name == "ELU":
-                mods.append(nn.ELU())
-            else:
-                raise ValueError(f"RecurrentPolicy.from_exported: actor.{k} is {name}; only Linear and ELU are supported")
-        norm = None
-        if "normalizer._mean" in sd:
-            norm = EmpiricalNormalization([sd["normalizer._mean"].shape[-1]],
-                                          eps=float(getattr(jit_module.normalizer, "eps", 1e-2)))
-            norm.load_state_dict({k.split(".", 1)[1]: v for k, v in sd.items() if k.startswith("normalizer.")})
-            norm.eval()
+        actor, norm = _exported_actor(jit_module, sd), _exported_normalizer(jit_module, sd)
         if device is None:
             device = w_ih.device
-        actor = nn.Sequential(*mods).to(device).eval()
-        rnn = rnn.to(device).eval()
-        for p in list(actor.parameters()) + list(rnn.parameters()):
-            p.requires_grad_(False)
-        p = cls(rnn, actor, norm.to(device) if norm is not None else None, fused=fused)
+        rnn = rnn.to(device).eval().requires_grad_(False)
+        p = cls(rnn, actor.to(device), norm.to(device) if norm is not None else None, fused=fused)
         p._ensure_state(num_envs, torch.device(device))
         return p
 

@@ -32,6 +32,8 @@ import torch.nn as nn
 from torch.distributions import Normal
 
 from . import distributed as D
+from .graphs import TrainingState, capture, graph_enabled
+from .policy import FusedActorCritic, fused_collection_on
 from .recurrent import Memory, split_and_pad_trajectories, state_tensors
 
 
@@ -456,6 +458,7 @@ class PPO:
         self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
                                           fused=fused, capturable=fused)
         self._graph = None
+        self._fused = None
         self.learning_rate = learning_rate
         self.num_learning_epochs = num_learning_epochs
         self.num_mini_batches = num_mini_batches
@@ -552,7 +555,7 @@ class PPO:
         if self._act_graph_ok(obs, critic_obs):
             return self._act_graphed(obs, critic_obs)
         self._obs, self._critic_obs = obs, critic_obs
-        if self._act_fused_ok(obs):  # eager collection on the fused forward: the graphed body, run directly
+        if fused_collection_on(obs):  # eager collection on the fused forward: the graphed body, run directly
             with torch.no_grad():
                 out = self._act_compute(obs, critic_obs)
             self._actions, self._values, self._log_prob, self._mu, self._sigma = out
@@ -567,13 +570,8 @@ class PPO:
     # ---- collection as a HIP graph: actor + critic forward, Gaussian sample, log-probability in one launch
     def _act_graph_ok(self, obs, critic_obs) -> bool:
         # a recurrent policy's collection is captured on the fused step only: it updates the state in place
-        return (obs.is_cuda and not torch.is_grad_enabled() and os.environ.get("H12_PPO_GRAPH", "1") != "0"
-                and (not self.recurrent or self._act_fused_ok(obs)))
-
-    def _act_fused_ok(self, obs) -> bool:
-        from .policy import fused_collection_enabled
-
-        return fused_collection_enabled() and obs.is_cuda and not torch.is_grad_enabled()
+        return (obs.is_cuda and not torch.is_grad_enabled() and graph_enabled()
+                and (not self.recurrent or fused_collection_on(obs)))
 
     def _fused_states(self):
         """The (h, c) [N][H] views of the two memories' states for h12learn_lstm_step, which updates them in place.  A
@@ -599,47 +597,17 @@ class PPO:
             out.append((hs[0][0], hs[1][0]))
         return out
 
-    def _act_fused_recurrent(self, obs, cobs):
-        """H12_POLICY_FUSED=1 with a recurrent policy: LSTM cell and MLP of actor and critic from h12learn_lstm_step, one
-        two-network launch when both read the same observation, re-packed in the same body, the memories' states
-        updated in place."""
-        from .policy import FusedLSTMStep
-
-        p = self.policy
-        shared = cobs is obs
-        f = getattr(self, "_fused_rnn", None)
-        if f is None or f[0] != shared:
-            steps = ((FusedLSTMStep([(p.memory_a.rnn, p.actor), (p.memory_c.rnn, p.critic)]),) if shared else
-                     (FusedLSTMStep([(p.memory_a.rnn, p.actor)]), FusedLSTMStep([(p.memory_c.rnn, p.critic)])))
-            f = self._fused_rnn = (shared, steps)
-        sa, sc = self._fused_states()
-        if shared:
-            return f[1][0](obs, [sa, sc], repack=True)
-        return f[1][0](obs, [sa], repack=True)[0], f[1][1](cobs, [sc], repack=True)[0]
-
     def _act_fused(self, obs, cobs):
-        """H12_POLICY_FUSED=1: actor mean and critic value from h12learn_mlp_forward, one two-network launch when
-        actor and critic read the same observation.  The weights are re-packed in the same body (and so inside the
-        captured graph): they can never be stale after an update."""
-        from .policy import FusedMLP
-
-        if self.recurrent:
-            return self._act_fused_recurrent(obs, cobs)
-        shared = cobs is obs
-        f = getattr(self, "_fused_mlp", None)
-        if f is None or f[0] != shared:
-            nets = ((FusedMLP([self.policy.actor, self.policy.critic]),) if shared else
-                    (FusedMLP([self.policy.actor]), FusedMLP([self.policy.critic])))
-            f = self._fused_mlp = (shared, nets)
-        if shared:
-            return f[1][0](obs, repack=True)
-        return f[1][0](obs, repack=True)[0], f[1][1](cobs, repack=True)[0]
-
-    def _act_body(self):
-        self._ga_out = self._act_compute(self._ga_obs, self._ga_cobs)
+        """H12_POLICY_FUSED=1: actor mean and critic value from policy.FusedActorCritic; a recurrent policy's memories
+        are stepped in place on their own storage."""
+        if self._fused is None:
+            p = self.policy
+            self._fused = FusedActorCritic(p.actor, p.critic,
+                                           (p.memory_a.rnn, p.memory_c.rnn) if self.recurrent else None)
+        return self._fused(obs, cobs, self._fused_states() if self.recurrent else None)
 
     def _act_compute(self, obs, cobs):
-        fused = self._act_fused_ok(obs)
+        fused = fused_collection_on(obs)
         if fused:
             mean, values = self._act_fused(obs, cobs)
         else:
@@ -657,28 +625,16 @@ class PPO:
         states = [t for pair in self._fused_states() for t in pair] if self.recurrent else []
         key += tuple(t.data_ptr() for t in states)
         if getattr(self, "_ga", None) is None or self._ga_key != key:
-            # normal (not inference) tensors throughout: the graph's RNG state is updated outside inference mode
-            # the warm-up and capture consume exploration-noise draws: the generator state is put back after
-            # them, so the replays draw the same noise sequence as the eager path (graph-safe philox offsets)
-            rng_state = torch.cuda.get_rng_state(obs.device)
-            kept = [t.clone() for t in states]  # the warm-up steps a recurrent policy's state: put back below
+            # normal (not inference) tensors throughout: the graph's RNG state is updated outside inference mode.
+            # The warm-up steps a recurrent policy's state and consumes exploration-noise draws: capture() puts both
+            # back, so the replays draw the same noise sequence as the eager path (graph-safe philox offsets)
             with torch.inference_mode(False), torch.no_grad():
                 self._ga_obs = torch.zeros(obs.shape, dtype=obs.dtype, device=obs.device)
                 self._ga_cobs = (self._ga_obs if critic_obs is obs else
                                  torch.zeros(critic_obs.shape, dtype=critic_obs.dtype, device=obs.device))
-                s = torch.cuda.Stream(device=obs.device)
-                s.wait_stream(torch.cuda.current_stream(obs.device))
-                with torch.cuda.stream(s):
-                    for _ in range(2):
-                        self._act_body()
-                torch.cuda.current_stream(obs.device).wait_stream(s)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._act_body()
-            torch.cuda.set_rng_state(rng_state, obs.device)
-            for t, k in zip(states, kept):
-                t.copy_(k)
-            self._ga, self._ga_key = g, key
+                self._ga, self._ga_out = capture(lambda: self._act_compute(self._ga_obs, self._ga_cobs), obs.device,
+                                                 undo=states, rng=True)
+            self._ga_key = key
         self._ga_obs.copy_(obs)
         if critic_obs is not obs:
             self._ga_cobs.copy_(critic_obs)
@@ -884,47 +840,24 @@ class PPO:
 
     def _graph_ok(self) -> bool:
         return (self._lr_t is not None and self.shard.world == 1 and str(self.device).startswith("cuda")
-                and os.environ.get("H12_PPO_GRAPH", "1") != "0")
-
-    def _snapshot(self):
-        st = {}
-        for p in self.policy.parameters():
-            st[p] = {k: v.detach().clone() for k, v in self.optimizer.state.get(p, {}).items() if torch.is_tensor(v)}
-        return [p.detach().clone() for p in self.policy.parameters()], st, self._lr_t.clone()
-
-    def _restore(self, snap):
-        params, st, lr = snap
-        with torch.no_grad():
-            for p, v in zip(self.policy.parameters(), params):
-                p.copy_(v)
-            for p in self.policy.parameters():
-                for k, v in self.optimizer.state.get(p, {}).items():
-                    if torch.is_tensor(v):
-                        v.copy_(st[p][k]) if k in st[p] else v.zero_()  # lazily created by the warm-up: initial 0
-            self._lr_t.copy_(lr)
+                and graph_enabled())
 
     def _capture(self, b: dict, mb: int):
         """Capture one minibatch update as a HIP graph (replayed num_epochs x num_mini_batches times per
-        update): the ~300 kernel launches of a minibatch cost one graph launch.  Warm-up runs on a side
-        stream on the real parameters, which are restored bit-exactly before the capture."""
+        update): the ~300 kernel launches of a minibatch cost one graph launch.  The warm-up runs on the real
+        parameters; they, the optimiser state, the learning rate and the statistics are restored bit-exactly before
+        the capture."""
         self._g_idx = torch.zeros(mb, dtype=torch.long, device=self.device)
         self._g_stats = torch.zeros(self._n_stats, device=self.device)
         self.policy.distribution = None  # drop autograd graphs built on the default stream
-        snap = self._snapshot()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._minibatch(b, self._g_idx, self._g_stats)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        self.policy.distribution = None
-        self._restore(snap)
-        self._g_stats.zero_()
-        g = torch.cuda.CUDAGraph()
-        self.optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(g):
-            self._minibatch(b, self._g_idx, self._g_stats)
-        self._graph = g
+
+        def drop_graphs_and_grads():
+            self.policy.distribution = None
+            self.optimizer.zero_grad(set_to_none=True)
+
+        state = TrainingState(self.policy.parameters(), self.optimizer, [self._lr_t, self._g_stats])
+        self._graph, _ = capture(lambda: self._minibatch(b, self._g_idx, self._g_stats), self.device, undo=[state],
+                                 before_capture=drop_graphs_and_grads)
         self._graph_key = (mb, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in sorted(b.items())))
 
     def _update_recurrent(self):

@@ -51,6 +51,7 @@ def main(argv=None) -> int:
 
     import torch
 
+    from h12env.graphs import capture
     from h12env.ppo import PPO, ActorCriticRecurrent
 
     if not torch.cuda.is_available():
@@ -98,15 +99,7 @@ def main(argv=None) -> int:
                 a = policy.act(obs)
                 return a, policy.evaluate(obs), policy.get_actions_log_prob(a)
 
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(3):
-                    body()
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
+            g, _ = capture(body, dev)
             v = [timed_us(g.replay, args.reps) for _ in range(args.rounds)]
         result["torch_graphed"] = {"median_us": statistics.median(v), "min_us": min(v), "samples": len(v)}
     except Exception as e:  # noqa: BLE001  (whatever the capture raises is the finding)

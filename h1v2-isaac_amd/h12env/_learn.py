@@ -18,7 +18,9 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_ppo_head_rows", "h12learn_ppo_head_max_actions", "h12learn_ppo_head_workspace_bytes",
                  "h12learn_ppo_head", "h12learn_cleanrl_head_rows", "h12learn_cleanrl_head_workspace_bytes",
                  "h12learn_cleanrl_head", "h12learn_lstm_max_hidden", "h12learn_lstm_packed_bytes",
-                 "h12learn_lstm_pack", "h12learn_lstm_step", "h12learn_last_error"]
+                 "h12learn_lstm_pack", "h12learn_lstm_step", "h12learn_lstm_seq_packed_bytes",
+                 "h12learn_lstm_seq_pack", "h12learn_lstm_seq_forward", "h12learn_lstm_seq_backward",
+                 "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -57,6 +59,28 @@ class LstmIo(C.Structure):
     _fields_ = [("x", C.c_void_p), ("reset", C.c_void_p), ("n", C.c_longlong), ("h_in", C.c_void_p * LSTM_MAX_NETS),
                 ("c_in", C.c_void_p * LSTM_MAX_NETS), ("h_out", C.c_void_p * LSTM_MAX_NETS),
                 ("c_out", C.c_void_p * LSTM_MAX_NETS), ("y", C.c_void_p * LSTM_MAX_NETS)]
+
+
+class LstmSeqDesc(C.Structure):
+    """h12learn_lstm_seq_desc"""
+    _fields_ = [("n_nets", C.c_int), ("hidden", C.c_int), ("w_hh", C.c_void_p * LSTM_MAX_NETS)]
+
+
+class LstmSeqIo(C.Structure):
+    """h12learn_lstm_seq_io"""
+    _fields_ = [("T", C.c_int), ("reserved", C.c_int), ("n", C.c_longlong), ("dones", C.c_void_p),
+                ("zx", C.c_void_p * LSTM_MAX_NETS), ("h0", C.c_void_p * LSTM_MAX_NETS),
+                ("c0", C.c_void_p * LSTM_MAX_NETS), ("h_seq", C.c_void_p * LSTM_MAX_NETS),
+                ("c_seq", C.c_void_p * LSTM_MAX_NETS), ("gates", C.c_void_p * LSTM_MAX_NETS)]
+
+
+class LstmSeqGradIo(C.Structure):
+    """h12learn_lstm_seq_grad_io"""
+    _fields_ = [("T", C.c_int), ("reserved", C.c_int), ("n", C.c_longlong), ("dones", C.c_void_p),
+                ("dh_seq", C.c_void_p * LSTM_MAX_NETS), ("gates", C.c_void_p * LSTM_MAX_NETS),
+                ("c_seq", C.c_void_p * LSTM_MAX_NETS), ("c0", C.c_void_p * LSTM_MAX_NETS),
+                ("dz", C.c_void_p * LSTM_MAX_NETS), ("dh0", C.c_void_p * LSTM_MAX_NETS),
+                ("dc0", C.c_void_p * LSTM_MAX_NETS)]
 
 
 PPO_STD_SCALAR, PPO_STD_LOG = 0, 1
@@ -156,6 +180,14 @@ def learn_library():
     lib.h12learn_lstm_pack.restype = C.c_int
     lib.h12learn_lstm_step.argtypes = [C.POINTER(LstmDesc), vp, C.POINTER(LstmIo), vp]
     lib.h12learn_lstm_step.restype = C.c_int
+    lib.h12learn_lstm_seq_packed_bytes.argtypes = [C.POINTER(LstmSeqDesc)]
+    lib.h12learn_lstm_seq_packed_bytes.restype = C.c_size_t
+    lib.h12learn_lstm_seq_pack.argtypes = [C.POINTER(LstmSeqDesc), vp, vp]
+    lib.h12learn_lstm_seq_pack.restype = C.c_int
+    lib.h12learn_lstm_seq_forward.argtypes = [C.POINTER(LstmSeqDesc), vp, C.POINTER(LstmSeqIo), vp]
+    lib.h12learn_lstm_seq_forward.restype = C.c_int
+    lib.h12learn_lstm_seq_backward.argtypes = [C.POINTER(LstmSeqDesc), vp, C.POINTER(LstmSeqGradIo), vp]
+    lib.h12learn_lstm_seq_backward.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -487,6 +519,118 @@ def lstm_step(desc: LstmDesc, packed: torch.Tensor, x: torch.Tensor, states, res
     _check(lib, lib.h12learn_lstm_step(C.byref(desc), packed.data_ptr(), C.byref(io), _stream(x.device)),
            "h12learn_lstm_step")
     return tuple(out)
+
+
+# ---- the recurrent policy's update (csrc/h12_policy_rnn_train.hip): LSTM over [T][n] with done resets, and its BPTT
+def lstm_seq_desc(w_hhs) -> LstmSeqDesc:
+    """The descriptor of the weight_hh [4H][H] tensors of 1..2 networks of one hidden size.  Shapes and data pointers
+    only; the caller keeps the tensors alive and in place."""
+    if not 1 <= len(w_hhs) <= LSTM_MAX_NETS:
+        raise ValueError(f"lstm_seq_desc: {len(w_hhs)} networks (1..{LSTM_MAX_NETS})")
+    d = LstmSeqDesc()
+    d.n_nets, d.hidden = len(w_hhs), int(w_hhs[0].shape[1])
+    for i, w in enumerate(w_hhs):
+        if _f32(w, f"w_hh[{i}]").shape != (4 * d.hidden, d.hidden):
+            raise ValueError(f"lstm_seq_desc: w_hh[{i}] {tuple(w.shape)} is not ({4 * d.hidden}, {d.hidden})")
+        d.w_hh[i] = w.data_ptr()
+    return d
+
+
+def lstm_seq_packed_bytes(desc: LstmSeqDesc) -> int:
+    lib = learn_library()
+    nbytes = lib.h12learn_lstm_seq_packed_bytes(C.byref(desc))
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_lstm_seq_packed_bytes")
+    return nbytes
+
+
+def lstm_seq_pack(desc: LstmSeqDesc, packed: torch.Tensor) -> torch.Tensor:
+    """One launch: W_hh and W_hh^T of every network of ``desc`` into ``packed`` (lstm_seq_packed_bytes)."""
+    lib = learn_library()
+    nbytes = lstm_seq_packed_bytes(desc)
+    if _f32(packed, "packed").numel() * 4 < nbytes:
+        raise ValueError("lstm_seq_pack: packed is smaller than lstm_seq_packed_bytes(desc)")
+    _check(lib, lib.h12learn_lstm_seq_pack(C.byref(desc), packed.data_ptr(), _stream(packed.device)),
+           "h12learn_lstm_seq_pack")
+    return packed
+
+
+def _seq_dones(dones: torch.Tensor, T: int, n: int, fn: str):
+    if not (dones.is_cuda and dones.dtype in (torch.uint8, torch.bool) and dones.is_contiguous()
+            and dones.shape == (T, n)):
+        raise ValueError(f"{fn}: dones must be a contiguous uint8 or bool CUDA tensor of ({T}, {n})")
+    return dones
+
+
+def _seq_same(ts, shape, name: str, fn: str):
+    for i, t in enumerate(ts):
+        if _f32(t, f"{name}[{i}]").shape != shape:
+            raise ValueError(f"{fn}: {name}[{i}] {tuple(t.shape)} is not {tuple(shape)}")
+
+
+def lstm_seq_forward(desc: LstmSeqDesc, packed: torch.Tensor, zxs, dones: torch.Tensor, h0s, c0s, out=None):
+    """One launch: per network (h_seq [T][n][H], c_seq [T][n][H], gates [T][n][4H]) from the input projections ``zxs``
+    ([T][n][4H] each), ``dones`` ([T][n] bytes) and the t = 0 states ``h0s`` / ``c0s`` ([n][H] each).  ``out``: the same
+    triples preallocated."""
+    lib = learn_library()
+    _f32(packed, "packed")
+    nn_, H = desc.n_nets, desc.hidden
+    if not (len(zxs) == len(h0s) == len(c0s) == nn_) or zxs[0].dim() != 3:
+        raise ValueError(f"lstm_seq_forward: {len(zxs)} projections, {len(h0s)} / {len(c0s)} states for {nn_} networks")
+    T, n = int(zxs[0].shape[0]), int(zxs[0].shape[1])
+    _seq_same(zxs, (T, n, 4 * H), "zxs", "lstm_seq_forward")
+    _seq_same(list(h0s) + list(c0s), (n, H), "states", "lstm_seq_forward")
+    _seq_dones(dones, T, n, "lstm_seq_forward")
+    dev = zxs[0].device
+    if out is None:
+        out = [tuple(torch.empty((T, n, w), dtype=torch.float32, device=dev) for w in (H, H, 4 * H))
+               for _ in range(nn_)]
+    io = LstmSeqIo()
+    io.T, io.n, io.dones = T, n, dones.data_ptr()
+    for i in range(nn_):
+        _seq_same(out[i][:2], (T, n, H), "out", "lstm_seq_forward")
+        _seq_same(out[i][2:], (T, n, 4 * H), "out", "lstm_seq_forward")
+        io.zx[i], io.h0[i], io.c0[i] = zxs[i].data_ptr(), h0s[i].data_ptr(), c0s[i].data_ptr()
+        io.h_seq[i], io.c_seq[i], io.gates[i] = (t.data_ptr() for t in out[i])
+    _check(lib, lib.h12learn_lstm_seq_forward(C.byref(desc), packed.data_ptr(), C.byref(io), _stream(dev)),
+           "h12learn_lstm_seq_forward")
+    return out
+
+
+def lstm_seq_backward(desc: LstmSeqDesc, packed: torch.Tensor, dh_seqs, saved, dones: torch.Tensor, c0s,
+                      need_state_grads: bool = True, out=None):
+    """One launch: per network (dz [T][n][4H], dh0 [n][H] or None, dc0 [n][H] or None) from ``dh_seqs`` ([T][n][H]
+    each) and ``saved``, per network the (c_seq, gates) of lstm_seq_forward.  ``out``: the same triples preallocated."""
+    lib = learn_library()
+    _f32(packed, "packed")
+    nn_, H = desc.n_nets, desc.hidden
+    if not (len(dh_seqs) == len(saved) == len(c0s) == nn_) or dh_seqs[0].dim() != 3:
+        raise ValueError(f"lstm_seq_backward: {len(dh_seqs)} gradients, {len(saved)} saved for {nn_} networks")
+    T, n = int(dh_seqs[0].shape[0]), int(dh_seqs[0].shape[1])
+    _seq_same(dh_seqs, (T, n, H), "dh_seqs", "lstm_seq_backward")
+    _seq_same([s[0] for s in saved], (T, n, H), "c_seq", "lstm_seq_backward")
+    _seq_same([s[1] for s in saved], (T, n, 4 * H), "gates", "lstm_seq_backward")
+    _seq_same(c0s, (n, H), "c0s", "lstm_seq_backward")
+    _seq_dones(dones, T, n, "lstm_seq_backward")
+    dev = dh_seqs[0].device
+    if out is None:
+        out = [(torch.empty((T, n, 4 * H), dtype=torch.float32, device=dev),
+                torch.empty((n, H), dtype=torch.float32, device=dev) if need_state_grads else None,
+                torch.empty((n, H), dtype=torch.float32, device=dev) if need_state_grads else None)
+               for _ in range(nn_)]
+    io = LstmSeqGradIo()
+    io.T, io.n, io.dones = T, n, dones.data_ptr()
+    for i in range(nn_):
+        dz, dh0, dc0 = out[i]
+        _seq_same([dz], (T, n, 4 * H), "dz", "lstm_seq_backward")
+        _seq_same([t for t in (dh0, dc0) if t is not None], (n, H), "dh0 / dc0", "lstm_seq_backward")
+        io.dh_seq[i], io.c_seq[i], io.gates[i] = dh_seqs[i].data_ptr(), saved[i][0].data_ptr(), saved[i][1].data_ptr()
+        io.c0[i], io.dz[i] = c0s[i].data_ptr(), dz.data_ptr()
+        io.dh0[i] = None if dh0 is None else dh0.data_ptr()
+        io.dc0[i] = None if dc0 is None else dc0.data_ptr()
+    _check(lib, lib.h12learn_lstm_seq_backward(C.byref(desc), packed.data_ptr(), C.byref(io), _stream(dev)),
+           "h12learn_lstm_seq_backward")
+    return out
 
 
 # ---- fused loss heads (csrc/h12_ppo_head.hip): what ppo_head and cleanrl_head check and allocate alike

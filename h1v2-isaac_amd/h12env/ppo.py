@@ -215,14 +215,25 @@ class ActorCriticRecurrent(ActorCritic):
         self.memory_a.reset(dones)
         self.memory_c.reset(dones)
 
-    def act(self, obs, masks=None, hidden_states=None):
-        return super().act(self.memory_a(obs, masks, hidden_states).squeeze(0))
+    def act(self, obs, masks=None, hidden_states=None, dones=None):
+        return super().act(self.memory_a(obs, masks, hidden_states, dones=dones).squeeze(0))
 
     def act_inference(self, obs):
         return super().act_inference(self.memory_a(obs).squeeze(0))
 
-    def evaluate(self, critic_obs, masks=None, hidden_states=None):
-        return super().evaluate(self.memory_c(critic_obs, masks, hidden_states).squeeze(0))
+    def evaluate(self, critic_obs, masks=None, hidden_states=None, dones=None):
+        return super().evaluate(self.memory_c(critic_obs, masks, hidden_states, dones=dones).squeeze(0))
+
+    def act_and_evaluate_sequence(self, obs, critic_obs, dones, hidden_a, hidden_c):
+        """act(obs, dones=, hidden_states=hidden_a) and evaluate(critic_obs, dones=, hidden_states=hidden_c) with both
+        memories in one two-network call of the sequence kernels (h12env.recurrent.lstm_sequence_pair).  Returns the
+        value."""
+        from .recurrent import lstm_sequence_pair
+
+        ha, hc = lstm_sequence_pair((self.memory_a.rnn, self.memory_c.rnn), (obs, critic_obs), dones,
+                                    (hidden_a, hidden_c))
+        ActorCritic.act(self, ha)
+        return ActorCritic.evaluate(self, hc)
 
     def get_hidden_states(self):
         return self.memory_a.hidden_states, self.memory_c.hidden_states
@@ -392,6 +403,38 @@ class RolloutStorage:
                     out[k] = t[k][:, e0:e1]
                 yield out
 
+    def recurrent_env_mini_batch_generator(self, num_mini_batches: int, num_epochs: int = 8, memories=None):
+        """The sequence form of recurrent_mini_batch_generator: the same env split and order, nothing cut or padded, so
+        every yield has fixed shapes and nothing here reads a device value on the host.  Yields a dict: the
+        [T, e0:e1, ...] slices "observations", "critic_observations" and "dones" ([T, envs] bytes), the envs' t = 0
+        states "hidden_a" / "hidden_c" (per state tensor [layers, envs, H]; zeros for a memory that had not stepped), and
+        the same per-sample slices as recurrent_mini_batch_generator.  The networks read them through
+        h12env.recurrent.lstm_sequence, which zeroes the state after a done."""
+        t = self.t
+        N = self.num_envs
+        cobs = t["privileged_observations"] if "privileged_observations" in t else t["observations"]
+        dones = (t["dones"][:, :, 0] != 0).to(torch.uint8)
+        saved_states = []
+        for which in (0, 1):
+            saved = self.start_states[which] if getattr(self, "start_states", None) else None
+            if saved is None:
+                rnn = memories[which].rnn
+                n_state = 2 if isinstance(rnn, nn.LSTM) else 1
+                saved = tuple(torch.zeros(rnn.num_layers, N, rnn.hidden_size, device=self.device)
+                              for _ in range(n_state))
+            saved_states.append(saved)
+        mb = N // num_mini_batches
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                e0, e1 = i * mb, (i + 1) * mb
+                hidden = [tuple(s0[:, e0:e1] for s0 in saved) for saved in saved_states]
+                hidden = [h if len(h) > 1 else h[0] for h in hidden]
+                out = {"observations": t["observations"][:, e0:e1], "critic_observations": cobs[:, e0:e1],
+                       "dones": dones[:, e0:e1], "hidden_a": hidden[0], "hidden_c": hidden[1]}
+                for k in ("actions", "values", "returns", "advantages", "actions_log_prob", "mu", "sigma"):
+                    out[k] = t[k][:, e0:e1]
+                yield out
+
     def compute_returns(self, last_values, gamma, lam, normalize_advantage=True):
         """GAE(gamma, lambda) backwards over the T steps, bootstrapped by last_values."""
         t = self.t
@@ -445,7 +488,7 @@ class PPO:
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
                  symmetry_cfg: dict | None = None, fused_learner: bool | None = None, fused_loss: bool | None = None,
-                 **kwargs):
+                 fused_rnn_update: bool | None = None, **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
@@ -495,6 +538,25 @@ class PPO:
                     on = fused_loss_enabled()
                 if on:
                     raise ValueError(f"{name} is not supported with a recurrent policy ({type(policy).__name__})")
+        # opt-in: a recurrent policy's update in the sequence form (h12env.recurrent.lstm_sequence): the
+        # memories run over [T, envs of the minibatch] with the state zeroed after a done, on the h12learn_lstm_seq_*
+        # kernels on the GPU; no trajectories are cut or padded.  None reads H12_RNN_UPDATE_FUSED=1.  The default stays
+        # the library LSTM over padded trajectories.
+        if fused_rnn_update is None:
+            fused_rnn_update = os.environ.get("H12_RNN_UPDATE_FUSED", "0") == "1"
+        self.fused_rnn_update = bool(fused_rnn_update)
+        if self.fused_rnn_update:
+            from .recurrent import lstm_sequence_limit
+
+            if not self.recurrent:
+                raise ValueError(f"fused_rnn_update needs a recurrent policy, {type(policy).__name__} has no memory")
+            if precision == "bf16":
+                raise ValueError("fused_rnn_update: the sequence kernels are exact fp32, precision='bf16' is not "
+                                 "supported")
+            for name in ("memory_a", "memory_c"):
+                why = lstm_sequence_limit(getattr(self.policy, name).rnn)
+                if why:
+                    raise ValueError(f"fused_rnn_update: {name}: {why}")
         if self.fused_learner:
             if precision == "bf16":
                 raise ValueError("fused_learner: the fused kernels are exact fp32, precision='bf16' is not supported")
@@ -717,7 +779,9 @@ class PPO:
         schedule to _lr_t and, without symmetry, adds the statistics.
 
         ``rec`` (a recurrent policy; b and idx are then None): one yield of recurrent_mini_batch_generator.  The networks
-        run in batch mode over its padded trajectories; the per-sample tensors are its [T, envs, ...] slices."""
+        run in batch mode over its padded trajectories; the per-sample tensors are its [T, envs, ...] slices.  With
+        fused_rnn_update it is one yield of recurrent_env_mini_batch_generator (no "masks") and the memories run in
+        sequence mode."""
         sym = self.symmetry
         fused = self.fused_loss
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
@@ -751,7 +815,14 @@ class PPO:
                                                                     (old_log_prob, target_values, advantages, returns))
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16, cache_enabled=False,
                             enabled=self.precision == "bf16" and str(self.device).startswith("cuda")):
-            if rec is not None:  # batch mode: the library LSTM over the padded trajectories, from their start states
+            if rec is not None and "masks" not in rec:  # sequence mode (fused_rnn_update): [T, envs], reset after a done
+                if obs.is_cuda:  # both memories in one two-network call
+                    value = self.policy.act_and_evaluate_sequence(obs, critic_obs, rec["dones"], rec["hidden_a"],
+                                                                  rec["hidden_c"]).float()
+                else:
+                    self.policy.act(obs, dones=rec["dones"], hidden_states=rec["hidden_a"])
+                    value = self.policy.evaluate(critic_obs, dones=rec["dones"], hidden_states=rec["hidden_c"]).float()
+            elif rec is not None:  # batch mode: the library LSTM over the padded trajectories, from their start states
                 self.policy.act(obs, masks=rec["masks"], hidden_states=rec["hidden_a"])
                 value = self.policy.evaluate(critic_obs, masks=rec["masks"], hidden_states=rec["hidden_c"]).float()
             else:
@@ -861,12 +932,15 @@ class PPO:
         self._graph_key = (mb, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in sorted(b.items())))
 
     def _update_recurrent(self):
-        """The update of a recurrent policy: eager (the number of trajectories changes every iteration, so there is
-        no graph to capture), minibatches over envs from recurrent_mini_batch_generator."""
+        """The update of a recurrent policy: eager, minibatches over envs.  From recurrent_mini_batch_generator the
+        number of trajectories changes every iteration, so there is no graph to capture; with fused_rnn_update the
+        shapes are fixed (recurrent_env_mini_batch_generator), and capturing it is left for later."""
         stats = torch.zeros(self._n_stats, device=self.device)
         n_updates = 0
         memories = (self.policy.memory_a, self.policy.memory_c)
-        for rec in self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs, memories):
+        generator = (self.storage.recurrent_env_mini_batch_generator if self.fused_rnn_update
+                     else self.storage.recurrent_mini_batch_generator)
+        for rec in generator(self.num_mini_batches, self.num_learning_epochs, memories):
             self._minibatch(None, None, stats, rec=rec)
             n_updates += 1
         return stats, n_updates

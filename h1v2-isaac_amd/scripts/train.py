@@ -62,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_learner", action="store_true", default=False,
                     help="the PPO update's actor and critic on the fused HIP forward / backward "
                          "(h12env.policy.TrainableFusedMLP; agent.algorithm.fused_learner=true works too)")
+    ap.add_argument("--fused_rnn_update", action="store_true", default=False,
+                    help="with --recurrent: the update's memories in the sequence form on the h12learn_lstm_seq_* kernels "
+                         "(h12env.recurrent.lstm_sequence; agent.algorithm.fused_rnn_update=true works too)")
     ap.add_argument("--fused_loss", action="store_true", default=False,
                     help="the PPO update's loss head (gathers, losses, gradients, KL schedule) as one fused HIP call "
                          "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
@@ -111,6 +114,8 @@ def apply_cli(agent_cfg, env_cfg, args):
         agent_cfg.algorithm.fused_learner = True
     if getattr(args, "fused_loss", False):
         agent_cfg.algorithm.fused_loss = True
+    if getattr(args, "fused_rnn_update", False):
+        agent_cfg.algorithm.fused_rnn_update = True
     if getattr(args, "privileged_critic", False):
         from h12env.cfg import enable_privileged_critic
 

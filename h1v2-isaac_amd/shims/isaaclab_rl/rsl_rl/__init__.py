@@ -61,6 +61,9 @@ class RslRlPpoAlgorithmCfg:
     fused_learner: bool | None = None
     # h12env.ppo extension: the update's loss head as one HIP call, h12env.ppo_head.PPOHead (None: H12_PPO_HEAD_FUSED)
     fused_loss: bool | None = None
+    # h12env.ppo extension: a recurrent policy's update in the sequence form on the h12learn_lstm_seq_* kernels
+    # (None: H12_RNN_UPDATE_FUSED)
+    fused_rnn_update: bool | None = None
 
 
 @dataclass

@@ -1,5 +1,5 @@
 /* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
- * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_ppo_head.hip).
+ * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_policy_rnn_train.hip, csrc/h12_ppo_head.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
@@ -231,6 +231,81 @@ int h12learn_lstm_pack(const h12learn_lstm_desc* desc, float* packed, void* stre
  * raises the kernel's limit, and fails with H12LEARN_E_HIP ("must be made outside a stream capture (warm up first)")
  * when its stream is capturing. */
 int h12learn_lstm_step(const h12learn_lstm_desc* desc, const float* packed, const h12learn_lstm_io* io, void* stream);
+
+/* ---- the recurrent policy's update (csrc/h12_policy_rnn_train.hip): one LSTM layer run over a whole rollout
+ * [T][n] with the state zeroed after a done, and its back-propagation through time, one launch each, for up to
+ * H12LEARN_LSTM_MAX_NETS networks (the actor's and the critic's memories) over the same T, n, hidden size and dones.
+ * Exact fp32 on the design of h12learn_mlp_forward; hidden size 1 .. h12learn_lstm_max_hidden(), 1 <= T <= 4096, n >= 1.
+ *
+ * The caller's GEMM library makes the input projection zx = x W_ih^T + b_ih + b_hh ([T][n][4 hidden]) and, from dz, the
+ * weight gradients (dW_ih = dz^T x, dW_hh = dz^T h_prev with h_prev the reset-masked, shifted h_seq, db = sum dz).
+ *
+ * Forward, gate order i, f, g, o (torch's), for t = 0 .. T-1:
+ *     reset(t, r) = t >= 1 && dones[t-1][r] != 0         dones[T-1] is never read; t = 0 always reads h0 / c0
+ *     h_prev, c_prev = 0 where reset, else h_seq[t-1], c_seq[t-1] (h0, c0 at t = 0)
+ *     z = zx[t] + h_prev W_hh^T                           a bias-free k chain over h_prev from zero, THEN + zx
+ *     i, f, o = sigmoid(z_i), sigmoid(z_f), sigmoid(z_o);  g = tanh(z_g)         (1 / (1 + expf(-z)), true division)
+ *     c_seq[t] = f c_prev + i g;   h_seq[t] = o tanh(c_seq[t]);   gates[t] = (i, f, g, o)   the activated gates
+ * Backward, for t = T-1 .. 0, the carries dh_c, dc_c starting at zero:
+ *     dh = dh_seq[t] + dh_c;   do = dh tanh(c_t);   dc = dc_c + dh o (1 - tanh(c_t)^2)
+ *     di = dc g;  dg = dc i;  df = dc c_prev
+ *     dz[t] = (di i (1 - i), df f (1 - f), dg (1 - g^2), do o (1 - o))
+ *     dc_c = dc f;   dh_c = dz[t] W_hh                    a k chain over the 4 hidden columns from zero
+ *     where reset(t, r): dh_c = dc_c = 0                  a reset row sends nothing further back
+ * dh0 / dc0 (each may be null) receive the carries after t = 0.
+ *
+ * A block owns 16 rows for all T steps and the rows are independent: an output element's summation order depends on
+ * the hidden size alone, never on n, T, the row's place in its tile or the grid; no atomics; every output is bitwise
+ * reproducible.  All tensors contiguous; no output may overlap an input.  A hidden size above 160 needs more than
+ * 64 KiB of LDS: the first such call of each kernel raises its limit, and fails with H12LEARN_E_HIP ("must be made
+ * outside a stream capture (warm up first)") when its stream is capturing. */
+typedef struct h12learn_lstm_seq_desc {
+  int n_nets; /* 1 .. H12LEARN_LSTM_MAX_NETS */
+  int hidden;
+  const float* w_hh[H12LEARN_LSTM_MAX_NETS]; /* [4 hidden][hidden], read only by h12learn_lstm_seq_pack */
+} h12learn_lstm_seq_desc;
+
+typedef struct h12learn_lstm_seq_io {
+  int T;
+  int reserved; /* 0 */
+  long long n;
+  const unsigned char* dones;                 /* [T][n] bytes, shared by the networks */
+  const float* zx[H12LEARN_LSTM_MAX_NETS];    /* [T][n][4 hidden] */
+  const float* h0[H12LEARN_LSTM_MAX_NETS];    /* [n][hidden] */
+  const float* c0[H12LEARN_LSTM_MAX_NETS];    /* [n][hidden] */
+  float* h_seq[H12LEARN_LSTM_MAX_NETS];       /* [T][n][hidden] */
+  float* c_seq[H12LEARN_LSTM_MAX_NETS];       /* [T][n][hidden], kept for the backward */
+  float* gates[H12LEARN_LSTM_MAX_NETS];       /* [T][n][4 hidden], kept for the backward */
+} h12learn_lstm_seq_io;
+
+typedef struct h12learn_lstm_seq_grad_io {
+  int T;
+  int reserved; /* 0 */
+  long long n;
+  const unsigned char* dones;                  /* [T][n] bytes */
+  const float* dh_seq[H12LEARN_LSTM_MAX_NETS]; /* [T][n][hidden] */
+  const float* gates[H12LEARN_LSTM_MAX_NETS];  /* as the forward wrote them */
+  const float* c_seq[H12LEARN_LSTM_MAX_NETS];
+  const float* c0[H12LEARN_LSTM_MAX_NETS];
+  float* dz[H12LEARN_LSTM_MAX_NETS];           /* [T][n][4 hidden] */
+  float* dh0[H12LEARN_LSTM_MAX_NETS];          /* [n][hidden], or null */
+  float* dc0[H12LEARN_LSTM_MAX_NETS];          /* [n][hidden], or null */
+} h12learn_lstm_seq_grad_io;
+
+/* Bytes of the pack of desc (shapes only): per network W_hh in the layout of h12learn_mlp_pack (K = hidden padded to 16,
+ * 4 hidden output rows, no bias), then W_hh^T as h12learn_mlp_pack_t lays a layer out (K = 4 hidden padded to 16, hidden
+ * output rows).  0 with h12learn_last_error set when the shapes are invalid. */
+size_t h12learn_lstm_seq_packed_bytes(const h12learn_lstm_seq_desc* desc);
+
+/* One launch: both operands of every network into packed (16-byte aligned, h12learn_lstm_seq_packed_bytes).  Run it
+ * after every change of the weights; it may be captured. */
+int h12learn_lstm_seq_pack(const h12learn_lstm_seq_desc* desc, float* packed, void* stream);
+
+/* One launch each, grid (row tiles of 16, networks), from the weights in packed (desc.w_hh is not read). */
+int h12learn_lstm_seq_forward(const h12learn_lstm_seq_desc* desc, const float* packed, const h12learn_lstm_seq_io* io,
+                              void* stream);
+int h12learn_lstm_seq_backward(const h12learn_lstm_seq_desc* desc, const float* packed,
+                               const h12learn_lstm_seq_grad_io* io, void* stream);
 
 /* ---- fused PPO loss head (csrc/h12_ppo_head.hip): everything PPO._minibatch (h12env/ppo.py) computes between the
  * networks' outputs and loss.backward(), in two launches: the minibatch gathers of the per-sample tensors, the Gaussian

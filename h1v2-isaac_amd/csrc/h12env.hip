@@ -545,23 +545,25 @@ H12_DEV bool contact_sphere(const KParams& P, const float Rb[3][3], const float*
 // needs no square root or reciprocal.  (Far beyond that range -- a diverging state -- the polynomials can overflow; such
 // a base is terminated by base_diverged at the end of the env step.)  w = 0 leaves q as it is (the oracle's rule)
 H12_DEV void quat_integrate(float* q, const float* w, float h) {
+  // without a branch: the rotated quaternion is computed for every lane and selected on w2 > 0 (a lane at rest keeps
+  // its q bit for bit, as under the branch this replaced: that one cost the physics wave an exec-mask region, and a
+  // basic-block boundary, between the state read-back and put_state)
   const float w2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  if (w2 > 0.f) {
-    const float a2 = w2 * (0.25f * h * h);
-    // sin(a) / a and cos(a) to a^8
-    const float sa = __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, 1.f / 362880.f,
-                              -1.f / 5040.f), 1.f / 120.f), -1.f / 6.f), 1.f);
-    const float ch = __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, 1.f / 40320.f,
-                              -1.f / 720.f), 1.f / 24.f), -0.5f), 1.f);
-    const float sh = sa * (0.5f * h);
-    float r[4] = {ch, w[0] * sh, w[1] * sh, w[2] * sh};
-    float o[4] = {q[0] * r[0] - q[1] * r[1] - q[2] * r[2] - q[3] * r[3],
-                  q[0] * r[1] + q[1] * r[0] + q[2] * r[3] - q[3] * r[2],
-                  q[0] * r[2] - q[1] * r[3] + q[2] * r[0] + q[3] * r[1],
-                  q[0] * r[3] + q[1] * r[2] - q[2] * r[1] + q[3] * r[0]};
-    float inv = __builtin_amdgcn_rsqf(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3]);
-    q[0] = o[0] * inv; q[1] = o[1] * inv; q[2] = o[2] * inv; q[3] = o[3] * inv;
-  }
+  const float a2 = w2 * (0.25f * h * h);
+  // sin(a) / a and cos(a) to a^8
+  const float sa = __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, 1.f / 362880.f,
+                            -1.f / 5040.f), 1.f / 120.f), -1.f / 6.f), 1.f);
+  const float ch = __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, __builtin_fmaf(a2, 1.f / 40320.f,
+                            -1.f / 720.f), 1.f / 24.f), -0.5f), 1.f);
+  const float sh = sa * (0.5f * h);
+  float r[4] = {ch, w[0] * sh, w[1] * sh, w[2] * sh};
+  float o[4] = {q[0] * r[0] - q[1] * r[1] - q[2] * r[2] - q[3] * r[3],
+                q[0] * r[1] + q[1] * r[0] + q[2] * r[3] - q[3] * r[2],
+                q[0] * r[2] - q[1] * r[3] + q[2] * r[0] + q[3] * r[1],
+                q[0] * r[3] + q[1] * r[2] - q[2] * r[1] + q[3] * r[0]};
+  float inv = __builtin_amdgcn_rsqf(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3]);
+  const bool turn = w2 > 0.f;
+  for (int i = 0; i < 4; ++i) q[i] = turn ? o[i] * inv : q[i];
 }
 
 // Solve the 6x6 SPD system I x = b (LDL^T, fully unrolled)
@@ -1494,6 +1496,7 @@ struct HelpLds {
   float4 jt[4][BLOCK];    // knee contact: wrench (6), reported force (3), ImplC (5), z (1); spare (1)
   float4 bias_h[6][BLOCK];  // helper: bias forces b_0..b_2 (18), base body bias force (6; lane 0, else 0)
   float4 bias_c[5][BLOCK];  // contact wave: bias forces b_3..b_5 (18; the knee / sole added inertias' M a^v in), spare
+                          // (each link's six values in pair order, bias_pair_slot: a0 l0 a1 l1 a2 l2)
   float4 cw1[2][11][BLOCK];  // before R1, per half of the soles (spheres 0-1: helper; 2-3: contact wave): their added
                           // inertia (AInertia, 21), minus their wrench (6), their force (3, body coords), the implicit
                           // report (flat: sum beta, sum gamma, sum beta p, sum gamma p, u = 11; terrain: beta[2],
@@ -1636,6 +1639,10 @@ H12_DEV void get4(const float4 (*src)[BLOCK], int l, float* x, int n4) {
   const float (*d)[BLOCK] = reinterpret_cast<const float (*)[BLOCK]>(src);
   for (int i = 0; i < 4 * n4; ++i) x[i] = d[i][l];
 }
+// Slot order of one link's bias force [ang0..2, lin0..2] in bias_h / bias_c: (angular_k, linear_k) side by side, so one
+// ds_read2st64_b32 of the physics wave returns the register pair its packed bias chain consumes (in component order
+// every pair was assembled with a v_mov); the writers' ds_write2st64_b32 take any two registers
+H12_DEV constexpr int bias_pair_slot(int i) { return i < 3 ? 2 * i : 2 * (i - 3) + 1; }
 H12_DEV void put_state(int l, const Base& b, const Leg& lg, const float* org) {
   float x[32] = {b.pos[0], b.pos[1], b.pos[2], b.quat[0], b.quat[1], b.quat[2], b.quat[3],
                  b.vlin[0], b.vlin[1], b.vlin[2], b.wang[0], b.wang[1], b.wang[2]};
@@ -2098,7 +2105,13 @@ H12_DEV void helper_wave(const KParams& P, int n, int n_steps, uint32_t g, uint3
       AInertia Rg;
       base_body<K>(P, lg, v0, Rg, o + 18);
       if (leg) for (int i = 18; i < 24; ++i) o[i] = 0.f;
-      put4(H.bias_h, l, o, 6);
+      {
+        float op[24];
+        for (int j = 0; j < 3; ++j)
+          for (int i = 0; i < 6; ++i) op[6 * j + bias_pair_slot(i)] = o[6 * j + i];
+        for (int i = 18; i < 24; ++i) op[i] = o[i];
+        put4(H.bias_h, l, op, 6);
+      }
       if constexpr (!Feat<K>::terrain) helper_torso<K>(P, l, leg, b, vb, R0, pb0, org);
     }
     fuse_drain(fc, it);
@@ -2179,8 +2192,13 @@ H12_DEV void contact_wave(const KParams& P, int n, int n_steps, const FuseCtx& f
         ai_mul(dI, av, ma);
         for (int i = 0; i < 6; ++i) o[12 + i] += ma[i];
       }
-      o[18] = o[19] = 0.f;
-      put4(H.bias_c, l, o, 5);
+      {
+        float op[20];
+        for (int j = 0; j < 3; ++j)
+          for (int i = 0; i < 6; ++i) op[6 * j + bias_pair_slot(i)] = o[6 * j + i];
+        op[18] = op[19] = 0.f;
+        put4(H.bias_c, l, op, 5);
+      }
       float w[12];
       for (int i = 0; i < 6; ++i) { w[i] = av3[i]; w[6 + i] = av[i]; }
       put4(H.cw2, l, w, 3);
@@ -2446,6 +2464,9 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
     joint_terms(P, lg, h, tq, dl);
     for (int k = 0; k < NL; ++k) tau[k] = tau_pd[k] + tq[k];
   }
+  // the joint sines / cosines stay ahead of R1, where this wave has slack (else the compiler sinks most of them behind
+  // the barrier, into the inertia chain it runs alone: 8-12 transcendentals, two issue slots each)
+  for (int k = 0; k < NL; ++k) { pin(cs[k][0]); pin(cs[k][1]); }
   PHX(10);
   SYNC_W(1);  // R1: sole contacts (helper), knee contact (contact wave)
   PHX(8);
@@ -2496,8 +2517,9 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
     get4(H.bias_h, threadIdx.x, o, 6);
     get4(H.bias_c, threadIdx.x, c, 5);
     for (int i = 0; i < 6; ++i) {
-      pbias[0][i] = o[i]; pbias[1][i] = o[6 + i]; pbias[2][i] = o[12 + i]; pbase[i] = o[18 + i];
-      pbias[3][i] = c[i]; pbias[4][i] = c[6 + i]; pbias[5][i] = c[12 + i];
+      const int s = bias_pair_slot(i);
+      pbias[0][i] = o[s]; pbias[1][i] = o[6 + s]; pbias[2][i] = o[12 + s]; pbase[i] = o[18 + i];
+      pbias[3][i] = c[s]; pbias[4][i] = c[6 + s]; pbias[5][i] = c[12 + s];
     }
   }
   AInertia Rg;  // base body inertia (lane 0)
@@ -2517,6 +2539,7 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
                         : pk2(pbias[j][k], pbias[j][3 + k]);
   // ---- pass 2, bias-force chain (leaf -> root), on (angular, linear) pairs
   float pAcc[6];
+  float t[16];  // the torso contact's hand-off, used behind the chain
   {
     float pa[8], pc[8];
     get4(&H.cw1[0][5], threadIdx.x, pa, 2);  // floats 20..27 of each half's hand-off: the soles' -wrench at 21..26
@@ -2528,6 +2551,9 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
     link_p_pk<4>(cs, U, Dinv, tau, pb, p, u);
     link_p_pk<3>(cs, U, Dinv, tau, pb, p, u);
     link_p_pk<2>(cs, U, Dinv, tau, pb, p, u);
+    // read under the chain's last two links (with the first batch behind R2 its 16 registers do not fit: .vgpr_count
+    // 321; behind the chain, where it is used, the lone wave sits out the LDS round trip)
+    get4(H.torso, threadIdx.x, t, 4);
     link_p_pk<1>(cs, U, Dinv, tau, pb, p, u);
     link_p_pk<0>(cs, U, Dinv, tau, pb, p, u);
     PHL(0);
@@ -2551,8 +2577,6 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
   {
     for (int i = 0; i < 6; ++i) pAcc[i] += pbase[i];
     torso_corner(R0, corner);
-    float t[16];
-    get4(H.torso, threadIdx.x, t, 4);
     for (int a = 0; a < 3; ++a) fr.torso[a] += t[6 + a];
     ict.beta = t[9]; ict.gamma = t[10]; ict.u[0] = t[11]; ict.u[1] = t[12]; ict.u[2] = t[13];
     const bool c = t[14] != 0.f;
@@ -2585,6 +2609,12 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
   // ---- pass 3 (root -> leaf) in the lane frame: a~ (the implicit contact reports use a~ + a^v)
   float avk[12];
   get4(H.cw2, threadIdx.x, avk, 3);
+  // the sole reports' hand-off (floats 28..43 of each half: the report at 30..) is read here, ahead of pass 3, and the
+  // step's start state (below) ahead of the sole report: read where they are used, each batch met a full lgkmcnt wait
+  // within a few instructions, an LDS round trip the lone physics wave sat out
+  float rs[2][16];
+  get4(&H.cw1[0][7], threadIdx.x, rs[0], 4);
+  get4(&H.cw1[1][7], threadIdx.x, rs[1], 4);
   f32x2 ap[3];  // (angular, linear) pairs
   for (int k = 0; k < 3; ++k) ap[k] = pk2(s6(k, sg) * a0[k], s6(3 + k, sg) * a0[3 + k]);
   float qdd[NL];
@@ -2601,11 +2631,12 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
   link_pass3_pk<4>(cs, U, Dinv, u, ap, qdd);
   link_pass3_pk<5>(cs, U, Dinv, u, ap, qdd);
   PHL(2);
+  float x[20];  // the step's start state (used by the integration below)
+  get4(H.st, threadIdx.x, x, 5);
   if (P.impl) {  // implicit part of the sole forces (a~ + a^v = the foot's acceleration, shifted frame)
-    float ah[6], r[2][16];
+    float ah[6];
+    const auto& r = rs;
     for (int k = 0; k < 3; ++k) { ah[k] = ap[k].x + avk[6 + k]; ah[3 + k] = ap[k].y + avk[9 + k]; }
-    get4(&H.cw1[0][7], threadIdx.x, r[0], 4);  // floats 28..43 of each half: the report at 30..
-    get4(&H.cw1[1][7], threadIdx.x, r[1], 4);
     if constexpr (!Feat<K>::terrain) {
       // without a branch: a sole out of contact reports zero sums (sole_handoff)
       SoleSums ss;
@@ -2629,8 +2660,6 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
   // joint angles are read back from the helper waves' LDS copy (put_state, the same floats): their registers die
   // after the sin / cos instead of being parked through the ABA passes
   {
-    float x[20];
-    get4(H.st, threadIdx.x, x, 5);
     for (int i = 0; i < 3; ++i) { b.pos[i] = x[i]; b.vlin[i] = x[7 + i]; b.wang[i] = x[10 + i]; }
     for (int i = 0; i < 4; ++i) b.quat[i] = x[3 + i];
     for (int k = 0; k < NL; ++k) lg.q[k] = x[13 + k];
@@ -2653,10 +2682,14 @@ H12_DEV void inner_step_hw(const KParams& P, int leg, Base& b, Leg& lg, const Pd
     lg.qd[k] += h * qdd[k];
     float q = lg.q[k] + h * lg.qd[k];
     // hard-limit residual (oracle limit_projection): beyond the range by more than lproj -> back to the tolerance,
-    // outward velocity zeroed; branch-free
+    // outward velocity zeroed.  Both clamped velocities are computed first and then selected: written as nested
+    // conditionals around the fminf / fmaxf calls, each joint compiled to an exec-mask diamond (7 scalar instructions
+    // and a branch around one v_min and one v_max) on the physics wave's solo tail
     const float hi = h12m::QHI[k] + P.lproj, lo = h12m::QLO[k] - P.lproj;
     const bool over = q > hi, under = q < lo;
-    lg.qd[k] = over ? fminf(lg.qd[k], 0.f) : (under ? fmaxf(lg.qd[k], 0.f) : lg.qd[k]);
+    const float qd_neg = fminf(lg.qd[k], 0.f), qd_pos = fmaxf(lg.qd[k], 0.f);
+    const float qd_under = under ? qd_pos : lg.qd[k];
+    lg.qd[k] = over ? qd_neg : qd_under;
     lg.q[k] = fminf(fmaxf(q, lo), hi);
   }
   if (more) {

@@ -95,8 +95,12 @@ PATCHES_HEAD: dict = {
     "chain_half": [("  link_ia<2, true>(P, lg, cs, v, ick, knee_pz, dl, IA, U, Dinv, Ic, h);\n"
                     "  link_ia<1, true>(P, lg, cs, v, ick, knee_pz, dl, IA, U, Dinv, Ic, h);\n"
                     "  link_ia<0, true>(P, lg, cs, v, ick, knee_pz, dl, IA, U, Dinv, Ic, h);\n", ""),
-                   ("    link_p_pk<2>(cs, U, Dinv, tau, pb, p, u);\n    link_p_pk<1>(cs, U, Dinv, tau, pb, p, u);\n"
-                    "    link_p_pk<0>(cs, U, Dinv, tau, pb, p, u);\n", ""),
+                   ("    link_p_pk<2>(cs, U, Dinv, tau, pb, p, u);\n"
+                    "    // read under the chain's last two links (with the first batch behind R2 its 16 registers do not "
+                    "fit: .vgpr_count\n    // 321; behind the chain, where it is used, the lone wave sits out the LDS round "
+                    "trip)\n    get4(H.torso, threadIdx.x, t, 4);\n"
+                    "    link_p_pk<1>(cs, U, Dinv, tau, pb, p, u);\n"
+                    "    link_p_pk<0>(cs, U, Dinv, tau, pb, p, u);\n", "    get4(H.torso, threadIdx.x, t, 4);\n"),
                    ("  link_pass3_pk<0>(cs, U, Dinv, u, ap, qdd);\n  link_pass3_pk<1>(cs, U, Dinv, u, ap, qdd);\n"
                     "  link_pass3_pk<2>(cs, U, Dinv, u, ap, qdd);\n", "  qdd[0] = qdd[1] = qdd[2] = 0.f;\n")],
     # probe: the episode sums loaded after the helper wave's loop (is their load the helper's delay at the first S?)
@@ -213,10 +217,18 @@ PATCHES_HEAD["siderod_probe"] = [("#pragma unroll\n  for (int q = Q0; q < Q1; ++
 PATCHES_HEAD["nan_selfcorr"] = [("leg_pass1<K, true>(leg, b, lg, org, R0, vb, pb0, cs, v, Rk, pk, R, p, true);",
                                  "leg_pass1<K, false>(leg, b, lg, org, R0, vb, pb0, cs, v, Rk, pk, R, p, true);")]
 PATCHES_HEAD["nan_nocorr"] = [("using namespace h12;\n", "using namespace h12;\n#define fsincos(x, s, c) fsincos_hw(x, s, c)\n")]
+# issue-slot pricing (profiles/slot_diet/): what one scalar issue slot costs the physics wave where it runs alone, right
+# behind barrier R2 -- 40 s_nop 0, or 40 s_mov_b32 to a dead SGPR (results unchanged; measured on commit 7b14028's kernel)
+_R2 = "  SYNC_W(2);  // R2: bias forces (helper: links 0-2 + base; contact wave: links 3-5), torso contact, self wrenches\n"
+PATCHES_HEAD["slot_nop40"] = [(_R2, _R2 + '  asm volatile(".rept 40\\n\\ts_nop 0\\n\\t.endr");\n')]
+PATCHES_HEAD["slot_smov40"] = [(_R2, _R2 + '  {\n    int dead;\n    asm volatile(".rept 40\\n\\ts_mov_b32 %0, 1\\n\\t.endr" '
+                                ': "=s"(dead));\n  }\n')]
 ALL = {**{k: (R4_BASE, v) for k, v in PATCHES.items()}, **{k: (None, v) for k, v in PATCHES_HEAD.items()}}
 # the CaT probes were measured on commit 306df83's kernel (profiles/r6/cat_inline_ab.txt)
 for _k in ("cat_nowait", "cat_nochain", "cat_floor", "cat_fold_after_f", "cat_no_nmrows"):
     ALL[_k] = ("306df83", ALL[_k][1])
+for _k in ("slot_nop40", "slot_smov40"):
+    ALL[_k] = ("7b14028", ALL[_k][1])
 SOURCES = ("h1v2-isaac_amd/csrc/h12env.hip", "h1v2-isaac_amd/csrc/h12_math.h", "h1v2-isaac_amd/csrc/h12_model_gen.h",
            "include/h12env.h")
 

@@ -246,10 +246,41 @@ def enable_privileged_critic(env_cfg):
 
 
 @dataclass
+class StudentObsCfg:
+    """The deployable observation group a distilled student reads as extras["observations"]["student"] (h12env.student,
+    DESIGN.md section 7s): the Flat policy frame -- base_ang_vel, projected_gravity, velocity_commands, joint_pos,
+    joint_vel, actions, what the robot measures -- as (value + U(-n, n)) * scale per term, no clip, with a term-major
+    history of history_length (1 .. 10) frames.  The defaults are the Flat task's noise and no scaling."""
+    enable_corruption: bool = True
+    concatenate_terms: bool = True
+    history_length: int = 1
+    base_ang_vel: Unoise | None = field(default_factory=lambda: Unoise(-0.2, 0.2))
+    projected_gravity: Unoise | None = field(default_factory=lambda: Unoise(-0.05, 0.05))
+    velocity_commands: Unoise | None = None
+    joint_pos: Unoise | None = field(default_factory=lambda: Unoise(-0.01, 0.01))
+    joint_vel: Unoise | None = field(default_factory=lambda: Unoise(-1.5, 1.5))
+    actions: Unoise | None = None
+    scales: dict = field(default_factory=dict)
+
+
+def enable_student_observations(env_cfg, history_length: int | None = None):
+    """The scripts' --distill: switch the env cfg's student observation group on (defaults, or the given history)."""
+    obs = getattr(env_cfg, "observations", None)
+    if obs is None or "student" not in getattr(obs, "__dataclass_fields__", {}):
+        raise ValueError("--distill: this task's env cfg has no student observation group")
+    if obs.student is None:
+        obs.student = StudentObsCfg()
+    if history_length is not None:
+        obs.student.history_length = int(history_length)
+
+
+@dataclass
 class ObservationsCfg:
     policy: PolicyObsCfg = field(default_factory=PolicyObsCfg)
     # None: no critic group (the critic reads the policy row); left out of the cfg dumps while it is None
     critic: CriticObsCfg | None = field(default=None, metadata={"omit_if_none": True})
+    # None: no student group (nothing is launched for it); left out of the cfg dumps while it is None
+    student: StudentObsCfg | None = field(default=None, metadata={"omit_if_none": True})
 
 
 @dataclass

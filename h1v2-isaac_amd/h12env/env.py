@@ -10,7 +10,8 @@ in packages/biped_tasks/biped_tasks/utils/cat/cat_env.py:95-193):
   cfg, observation_manager.group_obs_dim, action_manager.total_action_dim, unwrapped, close()
 
 With cfg.observations.critic set, the obs dicts also hold "critic": the privileged rows of h12env.priv (one more
-launch per step, behind the env's on the same stream).
+launch per step, behind the env's on the same stream).  With cfg.observations.student set they hold "student": the
+deployable rows of h12env.student (one more launch per step() / reset(); observe() / compute() return them unchanged).
 
 Every step is ONE launch of the fused HIP kernel in libh12env.so (no CPU fallback: a missing
 extension raises).  State lives in one device workspace owned by a torch uint8 tensor; fields are
@@ -154,6 +155,12 @@ class _ObservationManager:
             self.group_obs_dim["critic"] = (env.critic_obs_dim,)
             self.group_obs_concatenate["critic"] = True
             self.active_terms["critic"] = term_names(env.terrain is not None)
+        if env._stu is not None:  # the deployable group (h12env.student)
+            from .student import TERMS
+
+            self.group_obs_dim["student"] = (env.student_obs_dim,)
+            self.group_obs_concatenate["student"] = True
+            self.active_terms["student"] = list(TERMS)
 
     def compute(self):
         return self._env._groups(self._env._obs[self._env._k], False)
@@ -317,6 +324,7 @@ class H12VelocityEnv:
         self.terrain = None
         self._apply_startup()
         self._init_critic()
+        self._init_student()
         if self.terrain is not None:
             origins = self._field("ORIGIN").T  # moved in-kernel by the terrain curriculum
         else:
@@ -369,12 +377,52 @@ class H12VelocityEnv:
         if rc:
             check_priv(lib, rc, "h12priv_observe")
 
+    def _init_student(self):
+        """The deployable observation group (cfg.observations.student, h12env.student): its config struct and the two
+        row buffers the history lives in.  They swap on every push (step() / reset()) and only then, so they have an
+        index of their own: observe() swaps the policy's buffers and leaves these.  None when the group is off."""
+        self._stu = None
+        self.student_obs_dim = None
+        if self.cfg.observations.student is None:
+            return
+        from . import student
+
+        lib = student.student_library()
+        sc = student.student_config(self.cfg, self.env_offset)
+        self.student_obs_dim = student.FRAME * sc.history
+        self._stu_rows = [torch.zeros(self.num_envs, self.student_obs_dim, device=self.device) for _ in range(2)]
+        self._sk = 0
+        self._stu_resets = 0  # reset() pushes draw their noise at step index -1, -2, ...
+        self._stu = (lib, sc, C.byref(sc), student.check)
+
+    def _student_push(self, step_index: int, fill_all: bool = False, fill_mask: torch.Tensor | None = None):
+        """h12student_observe of the workspace as it stands: the previous rows shifted by one frame (or filled, where the
+        env was just reset) into the other buffer, which becomes the current one.  One launch behind the env's kernels
+        on the same stream, no host sync.  fill_mask ([n] uint8, a masked reset's): exactly its rows fill; without it
+        the workspace's since-reset bits decide, as after a step."""
+        lib, sc, ref, check_stu = self._stu
+        prev = None if fill_all else self._stu_rows[self._sk].data_ptr()
+        sc.fill_mask = None if fill_mask is None else fill_mask.data_ptr()
+        self._sk ^= 1
+        rc = lib.h12student_observe(self._state.data_ptr(), self.num_envs, ref, prev, self._stu_rows[self._sk].data_ptr(),
+                                    step_index, _raw_stream(self._dev_index))
+        sc.fill_mask = None  # the launch took the pointer as a kernel argument
+        if rc:
+            check_stu(lib, rc, "h12student_observe")
+
     def _groups(self, policy, copy):
-        """The observation dict: the policy rows and, with the privileged group on, the current critic rows."""
-        if self._priv is None:
+        """The observation dict: the policy rows and, with the privileged / deployable groups on, the current critic /
+        student rows."""
+        if self._priv is None and self._stu is None:
             return {"policy": policy}
-        c = self._crit[self._k]
-        return {"policy": policy, "critic": c.clone() if copy else c}
+        out = {"policy": policy}
+        if self._priv is not None:
+            c = self._crit[self._k]
+            out["critic"] = c.clone() if copy else c
+        if self._stu is not None:
+            r = self._stu_rows[self._sk]
+            out["student"] = r.clone() if copy else r
+        return out
 
     def _build_step_outs(self):
         """h12env_step output structs, one per observation buffer (their pointers never change), the log ring's
@@ -441,6 +489,8 @@ class H12VelocityEnv:
             groups = {"policy": gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,))}
             if self._priv is not None:
                 groups["critic"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.critic_obs_dim,))
+            if self._stu is not None:
+                groups["student"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.student_obs_dim,))
             self.single_observation_space = gym.spaces.Dict(groups)
             self.single_action_space = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(NJ,))
             self.observation_space = gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
@@ -453,6 +503,9 @@ class H12VelocityEnv:
             if self._priv is not None:
                 self.single_observation_space["critic"] = (self.critic_obs_dim,)
                 self.observation_space["critic"] = (self.num_envs, self.critic_obs_dim)
+            if self._stu is not None:
+                self.single_observation_space["student"] = (self.student_obs_dim,)
+                self.observation_space["student"] = (self.num_envs, self.student_obs_dim)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -544,6 +597,9 @@ class H12VelocityEnv:
         self._lib.h12env_destroy(self._h)
         self._h = h
         self._bind_terrain()
+        if self._stu is not None:  # the student group's noise is keyed by the env's seed
+            sc = self._stu[1]
+            sc.seed_lo, sc.seed_hi = self._ccfg.seed & 0xFFFFFFFF, self._ccfg.seed >> 32
         return int(seed)
 
     def reset(self, seed: int | None = None, env_ids=None, options=None):
@@ -560,6 +616,9 @@ class H12VelocityEnv:
         self.extras = {}
         if self._priv is not None:
             self._critic_rows()
+        if self._stu is not None:
+            self._stu_resets += 1
+            self._student_push(-self._stu_resets, fill_all=mask is None, fill_mask=mask)
         return self._groups(obs.clone() if self.obs_copy else obs, self.obs_copy), self.extras
 
     def step(self, action: torch.Tensor):
@@ -613,10 +672,13 @@ class H12VelocityEnv:
         self._live_logs[self.common_step_counter] = weakref.ref(log)
         self.extras = {"log": log, "time_outs": self.reset_time_outs}
         obs_out = obs.clone() if self.obs_copy else obs
-        if self._priv is None:
+        if self._priv is None and self._stu is None:
             obs_dict = {"policy": obs_out}
         else:
-            self._critic_rows()
+            if self._priv is not None:
+                self._critic_rows()
+            if self._stu is not None:
+                self._student_push(self.common_step_counter)
             obs_dict = self._groups(obs_out, self.obs_copy)
         if self._cat:  # CaTEnv.step: dones = constraint termination probability, 1 where reset (cat_env.py:153-193)
             return obs_dict, self.reward_buf, self._dones, self.reset_time_outs, self.extras
@@ -633,6 +695,8 @@ class H12VelocityEnv:
             raise ValueError("bind_rollout needs the flat observation layout (history) and a non-CaT task")
         if self._priv is not None:
             raise ValueError("bind_rollout with a critic observation group: the compact records carry no critic row")
+        if self._stu is not None:
+            raise ValueError("bind_rollout with a student observation group: the compact records carry no student row")
         if rec.n != self.num_envs or rec.history * 45 != self.obs_dim:
             raise ValueError("rollout recorder was built for another env shape")
         self._rollout_saved = (self.reward_buf, self.reset_terminated, self.reset_time_outs)
@@ -726,6 +790,8 @@ class H12VelocityEnv:
         if self._priv is not None:  # the critic rows and the foot forces the next reset() / observe() reads
             snap["critic"] = [c.clone() for c in self._crit]
             snap["foot_force"] = self.foot_contact_force.clone()
+        if self._stu is not None:  # both row buffers (the history), which one is current, and the reset-noise counter
+            snap["student"] = ([r.clone() for r in self._stu_rows], self._sk, self._stu_resets)
         return snap
 
     def restore(self, snap: dict):
@@ -737,6 +803,10 @@ class H12VelocityEnv:
             for c, s in zip(self._crit, snap["critic"]):
                 c.copy_(s)
             self.foot_contact_force.copy_(snap["foot_force"])
+        if self._stu is not None:
+            rows, self._sk, self._stu_resets = snap["student"]
+            for r, s in zip(self._stu_rows, rows):
+                r.copy_(s)
         self._k = snap["k"]
         self.common_step_counter = snap["counter"]
 

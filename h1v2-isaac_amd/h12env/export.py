@@ -39,12 +39,19 @@ _OBS_FUNCS = {  # cfg term -> isaaclab mdp function name (the env.yaml "name")
 
 
 # ---------------------------------------------------------------------------------------------- env.yaml
-def deploy_config(cfg) -> dict:
-    """get_deploy_config restated for H12FlatEnvCfg / H12RoughEnvCfg."""
-    po = cfg.observations.policy
+def deploy_config(cfg, group: str = "policy") -> dict:
+    """get_deploy_config restated for H12FlatEnvCfg / H12RoughEnvCfg.  ``group`` names the observation group the
+    exported policy reads: "policy" (the default, the actor's row), or "student" -- the deployable group of a distilled
+    student (cfg.observations.student, h12env.student): its six terms, every one of which the deploy stack's observation
+    handler serves, and its history_length, whatever the task's policy row holds."""
+    if group not in ("policy", "student"):
+        raise ValueError(f"deploy_config: group {group!r} (policy or student)")
+    po = getattr(cfg.observations, group, None)
+    if po is None:
+        raise ValueError(f"deploy_config: cfg.observations.{group} is not set")
     observations = []
     for term, fn in _OBS_FUNCS.items():
-        if term in ("base_lin_vel", "height_scan") and getattr(po, term, None) is None:
+        if term in ("base_lin_vel", "height_scan") and (group == "student" or getattr(po, term, None) is None):
             continue
         ent = {"name": fn}
         scale = getattr(po, "scales", {}).get(term, 1.0) if hasattr(po, "scales") else 1.0
@@ -77,10 +84,10 @@ def deploy_config(cfg) -> dict:
     }
 
 
-def write_env_yaml(cfg, path: str) -> str:
+def write_env_yaml(cfg, path: str, group: str = "policy") -> str:
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w") as f:
-        yaml.safe_dump(deploy_config(cfg), f, sort_keys=False, default_flow_style=False)
+        yaml.safe_dump(deploy_config(cfg, group), f, sort_keys=False, default_flow_style=False)
     return path
 
 

@@ -114,6 +114,11 @@ def lstm_sequence_torch(rnn: nn.Module, x: torch.Tensor, dones: torch.Tensor, hi
     """The definition, as a torch loop over t: ``rnn`` (any nn.LSTM / nn.GRU) stepped over x [T, N, d] from
     ``hidden_states`` ([layers, N, H] per state tensor), the state set to zero before step t wherever dones[t - 1] != 0.
     At every (t, env) this is what split_and_pad_trajectories -> rnn -> unpad_trajectories gives."""
+    return _sequence_loop(rnn, x, dones, hidden_states)[0]
+
+
+def _sequence_loop(rnn: nn.Module, x: torch.Tensor, dones: torch.Tensor, hidden_states):
+    """lstm_sequence_torch's loop: (the outputs [T, N, H], the state after the last step, in the module's layout)."""
     T, N = x.shape[:2]
     keep = (~_resets(dones, T, N)).to(x.dtype)[:, None, :, None]  # [T, 1, N, 1]
     state = hidden_states
@@ -123,7 +128,7 @@ def lstm_sequence_torch(rnn: nn.Module, x: torch.Tensor, dones: torch.Tensor, hi
             state = tuple(s * keep[t] for s in state) if isinstance(state, (tuple, list)) else state * keep[t]
         y, state = rnn(x[t:t + 1], state)
         out.append(y)
-    return torch.cat(out)
+    return torch.cat(out), state
 
 
 class _LstmSeq(torch.autograd.Function):
@@ -135,6 +140,12 @@ class _LstmSeq(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dones, *flat):
+        hs, _ = _LstmSeq._run(ctx, dones, *flat)
+        return hs if len(hs) > 1 else hs[0]
+
+    @staticmethod
+    def _run(ctx, dones, *flat):
+        """The forward: (the h_seq of every network, what h12learn_lstm_seq_forward returned per network)."""
         from . import _learn
 
         nets = [flat[i:i + _LstmSeq.PER_NET] for i in range(0, len(flat), _LstmSeq.PER_NET)]
@@ -151,8 +162,7 @@ class _LstmSeq(torch.autograd.Function):
         ctx.desc, ctx.packed, ctx.dones, ctx.n_nets = desc, packed, dones, len(nets)
         ctx.save_for_backward(*[t for i, n in enumerate(nets)
                                 for t in (xs[i], h0s[i], c0s[i], n[3], out[i][0], out[i][1], out[i][2])])
-        hs = tuple(o[0] for o in out)
-        return hs if len(hs) > 1 else hs[0]
+        return tuple(o[0] for o in out), out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -178,6 +188,23 @@ class _LstmSeq(torch.autograd.Function):
                     dh0 if need[base + 1] else None, dc0 if need[base + 2] else None,
                     dz2.t() @ x, dz2.t() @ h_prev, db, db]
         return tuple(res)
+
+
+class _LstmSeqState(_LstmSeq):
+    """_LstmSeq of one network that also returns c after the last step, [N, H], as a non-differentiable output: with
+    h_seq[-1] it is the state a following chunk of the sequence starts from (truncated BPTT detaches it anyway)."""
+
+    @staticmethod
+    def forward(ctx, dones, *flat):
+        (h_seq,), out = _LstmSeq._run(ctx, dones, *flat)
+        c_last = out[0][1][-1].clone()  # c_seq's last step: a copy, so that nothing holds a view of the saved tensor
+        ctx.mark_non_differentiable(c_last)
+        return h_seq, c_last
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh, _dc_last):
+        return _LstmSeq.backward(ctx, dh)
 
 
 def _as_seq_args(rnn, x, hidden_states):
@@ -217,3 +244,16 @@ def lstm_sequence_pair(rnns, xs, dones: torch.Tensor, hidden_states) -> tuple:
     T, N = xa.shape[:2]
     return _LstmSeq.apply(_seq_dones(dones, T, N), *_as_seq_args(ra, xa, hidden_states[0]),
                           *_as_seq_args(rc, xc, hidden_states[1]))
+
+
+def lstm_sequence_state(rnn: nn.Module, x: torch.Tensor, dones: torch.Tensor, hidden_states, kernels: bool = True):
+    """(h_seq, state after the last step) of lstm_sequence: the form a sequence that is cut into chunks needs, each chunk
+    starting from the state the previous one ended with.  The returned state is in the module's layout ((h, c) or h,
+    [layers, N, H]); dones[T - 1] is not applied to it -- the caller zeroes the rows that ended on the last step.
+    ``kernels`` False keeps the library rnn (the torch loop of the definition) even where the h12learn_lstm_seq_*
+    kernels could run; on them the state is detached (c after the last step is a by-product of the forward)."""
+    T, N = x.shape[:2]
+    if kernels and _kernels_admitted(rnn, x):
+        h_seq, c_last = _LstmSeqState.apply(_seq_dones(dones, T, N), *_as_seq_args(rnn, x, hidden_states))
+        return h_seq, (h_seq[-1].detach().unsqueeze(0), c_last.unsqueeze(0))
+    return _sequence_loop(rnn, x, dones, hidden_states)

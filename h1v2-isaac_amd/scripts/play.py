@@ -62,8 +62,23 @@ def main(argv=None) -> int:
     print(f"[INFO]: Loading model checkpoint from: {path}")
     # a recurrent checkpoint (train.py --recurrent) says so itself: the memory's type and size are read from it
     keys = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
-    recurrent = "memory_a.rnn.weight_ih_l0" in keys
-    if recurrent:
+    # a distilled student (train.py --distill) says so too: it has student.* parameters.  The env then returns the
+    # student observation group with the history the student was trained on, and the student is what plays
+    from h12env.distill import StudentView, cfg_from_checkpoint, is_student_checkpoint, student_group_from_run
+
+    student = is_student_checkpoint(keys)
+    student_policy = None
+    if student:
+        from isaaclab_rl.rsl_rl import RslRlDistillationAlgorithmCfg
+
+        student_policy, history = cfg_from_checkpoint(keys, agent_cfg.policy.activation)
+        # the group as the run trained on it (history, per-term scales: params/env.yaml of the run), and, as the Play
+        # tasks do for their policy group, without corruption
+        env_cfg.observations.student = student_group_from_run(os.path.dirname(path), history)
+        env_cfg.observations.student.enable_corruption = False
+        agent_cfg.algorithm = RslRlDistillationAlgorithmCfg()
+    recurrent = "memory_a.rnn.weight_ih_l0" in keys or (student and student_policy["class_name"].endswith("Recurrent"))
+    if recurrent and not student:
         w_ih, w_hh = keys["memory_a.rnn.weight_ih_l0"], keys["memory_a.rnn.weight_hh_l0"]
         agent_cfg.policy.class_name = "ActorCriticRecurrent"
         rnn = {"rnn_type": "lstm" if w_ih.shape[0] == 4 * w_hh.shape[1] else "gru", "rnn_hidden_dim": w_hh.shape[1],
@@ -76,23 +91,29 @@ def main(argv=None) -> int:
         env = gym.wrappers.RecordVideo(env, **vk)
     env = RslRlVecEnvWrapper(env)
     train_cfg = agent_cfg.to_dict()
-    if recurrent:
+    if student:
+        train_cfg["policy"] = student_policy
+    elif recurrent:
         train_cfg["policy"].update(rnn)
     runner = OnPolicyRunner(env, train_cfg, log_dir=None, device=args.device)
     runner.load(path)
     policy = runner.get_inference_policy(device=args.device, fused=args.fused)
     out = os.path.join(os.path.dirname(path), "exported")
-    export_policy_as_jit(runner.alg.policy, runner.obs_normalizer, out, "policy.pt")
-    write_env_yaml(env_cfg, os.path.join(out, "env.yaml"))
+    exported = StudentView(runner.alg.policy) if student else runner.alg.policy
+    export_policy_as_jit(exported, runner.obs_normalizer, out, "policy.pt")
+    write_env_yaml(env_cfg, os.path.join(out, "env.yaml"), group="student" if student else "policy")
     try:
-        export_policy_as_onnx(runner.alg.policy, runner.obs_normalizer, out, "policy.onnx")
+        export_policy_as_onnx(exported, runner.obs_normalizer, out, "policy.onnx")
     except (ImportError, NotImplementedError) as e:
         print(f"[INFO]: skipping ONNX export ({e})")
     print(f"[INFO]: exported to {out}")
-    obs, _ = env.get_observations()
+    # what the policy reads: the actor's row, or for a student its own observation group
+    pick = (lambda obs, extras: extras["observations"]["student"]) if student else (lambda obs, extras: obs)
+    obs = pick(*env.get_observations())
     with torch.inference_mode():
         for timestep in range(1, args.steps + 1):
-            obs, _, dones, _ = env.step(policy(obs))
+            obs, _, dones, extras = env.step(policy(obs))
+            obs = pick(obs, extras)
             if recurrent:  # forget the episodes that ended
                 (policy if args.fused else runner.alg.policy).reset(dones)
             if args.video and timestep == args.video_length:  # exit the play loop after recording one video

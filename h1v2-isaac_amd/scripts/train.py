@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""PPO training of an H1-2 velocity task on the MI355X env.
+"""PPO training of an H1-2 velocity task on the MI355X env, and (--distill) distillation of a trained policy into a
+student that reads only what the robot measures.
 
 Command line, configuration sources and log artefacts follow the reference's scripts/rsl_rl/train.py
 (+ cli_args.py): task / num_envs / seed / max_iterations / experiment_name / run_name / resume /
@@ -68,8 +69,78 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_loss", action="store_true", default=False,
                     help="the PPO update's loss head (gathers, losses, gradients, KL schedule) as one fused HIP call "
                          "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
+    ds = ap.add_argument_group("distillation", "rsl_rl's Distillation: a student on the deployable observation group "
+                               "(h12env.student) copies a PPO-trained teacher (h12env.distill)")
+    ds.add_argument("--distill", action="store_true", default=False,
+                    help="train a student by distillation: sets env.observations.student, swaps the agent's policy / "
+                         "algorithm sections for StudentTeacher / Distillation and loads --teacher_checkpoint; with "
+                         "--resume it continues a student run instead")
+    ds.add_argument("--teacher_checkpoint", type=str, default=None,
+                    help="model_<it>.pt of the PPO run whose actor is the teacher (same task, same policy sizes)")
+    ds.add_argument("--student_recurrent", action="store_true", default=False,
+                    help="StudentTeacherRecurrent: an LSTM memory in front of the student (agent.policy.rnn_* can be "
+                         "overridden); --fused_rnn_update runs its update on the h12learn_lstm_seq_* kernels")
+    ds.add_argument("--student_history", type=int, default=None,
+                    help="frames of history in the student's observation row (1 .. 10, default 1)")
     AppLauncher.add_app_launcher_args(ap)
     return ap
+
+
+def make_distillation(agent_cfg, env_cfg, args):
+    """--distill: the student observation group on the env cfg; the task's agent cfg with its policy section as a
+    StudentTeacher(Recurrent) cfg (teacher and student take the task's actor sizes and activation) and its algorithm
+    section as a Distillation cfg (the task's learning rate).  A recurrent teacher checkpoint says so itself: the
+    memory's type and size are read from it.  With --resume and no teacher checkpoint the student checkpoint that will
+    be resumed describes the run: network sizes, memories (a recurrent teacher's too) and the history length are read
+    from it (distill.cfg_from_checkpoint), and the observation group from the run's params/env.yaml."""
+    from h12env.cfg import enable_student_observations
+    from isaaclab_rl.rsl_rl import (RslRlDistillationAlgorithmCfg, RslRlDistillationStudentTeacherCfg,
+                                    RslRlDistillationStudentTeacherRecurrentCfg)
+
+    for flag in ("symmetry", "fused_learner", "fused_loss", "recurrent"):
+        if getattr(args, flag, None):
+            raise SystemExit(f"--distill does not take --{flag} (a PPO option; the student's memory is --student_recurrent)")
+    if not args.teacher_checkpoint and not args.resume:
+        raise SystemExit("--distill needs --teacher_checkpoint PATH (or --resume of a student run)")
+    old = agent_cfg.policy
+    if args.resume and not args.teacher_checkpoint:
+        import torch
+
+        from h12env.distill import cfg_from_checkpoint, is_student_checkpoint, student_group_from_run
+        from isaaclab_tasks.utils import get_checkpoint_path
+
+        root = os.path.abspath(os.path.join("logs", "rsl_rl", args.experiment_name or agent_cfg.experiment_name))
+        path = get_checkpoint_path(root, args.load_run or agent_cfg.load_run, args.checkpoint or agent_cfg.load_checkpoint)
+        keys = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
+        if not is_student_checkpoint(keys):
+            raise SystemExit(f"--distill --resume: {path} is not a student checkpoint (pass a PPO checkpoint as "
+                             "--teacher_checkpoint instead)")
+        policy, history = cfg_from_checkpoint(keys, old.activation)
+        if args.student_history not in (None, history):
+            raise SystemExit(f"--student_history {args.student_history}: the run being resumed has {history}")
+        env_cfg.observations.student = student_group_from_run(os.path.dirname(path), history)
+        recurrent = policy.pop("class_name") == "StudentTeacherRecurrent"
+        cls = RslRlDistillationStudentTeacherRecurrentCfg if recurrent else RslRlDistillationStudentTeacherCfg
+        agent_cfg.policy = cls(**policy)
+        agent_cfg.algorithm = RslRlDistillationAlgorithmCfg(learning_rate=agent_cfg.algorithm.learning_rate)
+        return
+    enable_student_observations(env_cfg, args.student_history)
+    kw = {"student_hidden_dims": list(old.actor_hidden_dims), "teacher_hidden_dims": list(old.actor_hidden_dims),
+          "activation": old.activation, "noise_std_type": old.noise_std_type}
+    if args.teacher_checkpoint:
+        import torch
+
+        keys = torch.load(args.teacher_checkpoint, map_location="cpu", weights_only=True)["model_state_dict"]
+        if "memory_a.rnn.weight_ih_l0" in keys:
+            if not args.student_recurrent:
+                raise SystemExit("--teacher_checkpoint is a recurrent policy: distil it with --student_recurrent")
+            w_ih, w_hh = keys["memory_a.rnn.weight_ih_l0"], keys["memory_a.rnn.weight_hh_l0"]
+            kw.update(teacher_recurrent=True, rnn_hidden_dim=w_hh.shape[1],
+                      rnn_type="lstm" if w_ih.shape[0] == 4 * w_hh.shape[1] else "gru",
+                      rnn_num_layers=len([k for k in keys if k.startswith("memory_a.rnn.weight_ih_l")]))
+    cls = RslRlDistillationStudentTeacherRecurrentCfg if args.student_recurrent else RslRlDistillationStudentTeacherCfg
+    agent_cfg.policy = cls(**kw)
+    agent_cfg.algorithm = RslRlDistillationAlgorithmCfg(learning_rate=agent_cfg.algorithm.learning_rate)
 
 
 def make_recurrent(agent_cfg):
@@ -155,7 +226,9 @@ def main(argv=None) -> int:
 
     env_cfg = load_cfg_from_registry(args.task, "env_cfg_entry_point")
     agent_cfg = load_cfg_from_registry(args.task, "rsl_rl_cfg_entry_point")
-    if args.recurrent:  # before the overrides, so that agent.policy.rnn_* exist for them
+    if args.distill:  # before the overrides, so that agent.algorithm.gradient_length etc. exist for them
+        make_distillation(agent_cfg, env_cfg, args)
+    elif args.recurrent:  # before the overrides, so that agent.policy.rnn_* exist for them
         make_recurrent(agent_cfg)
     apply_overrides(env_cfg, agent_cfg, hydra_args)
     apply_cli(agent_cfg, env_cfg, args)
@@ -180,6 +253,9 @@ def main(argv=None) -> int:
         path = get_checkpoint_path(root, agent_cfg.load_run, agent_cfg.load_checkpoint)
         print(f"[INFO]: Loading model checkpoint from: {path}")
         runner.load(path)
+    elif args.distill:  # a PPO checkpoint: its actor becomes the teacher, the student starts at iteration 0
+        print(f"[INFO]: Loading the teacher from: {args.teacher_checkpoint}")
+        runner.load(args.teacher_checkpoint)
     if rank == 0:
         for name, obj in (("env", env_cfg), ("agent", agent_cfg)):
             dump_yaml(os.path.join(log_dir, "params", f"{name}.yaml"), obj)

@@ -67,14 +67,50 @@ class RslRlPpoAlgorithmCfg:
 
 
 @dataclass
+class RslRlDistillationStudentTeacherCfg:
+    """rsl_rl's StudentTeacher (h12env.distill.StudentTeacher): the student MLP that is trained and the teacher MLP that
+    a PPO checkpoint's actor is loaded into."""
+    class_name: str = "StudentTeacher"
+    init_noise_std: float = 0.1
+    noise_std_type: str = "scalar"
+    student_hidden_dims: list = field(default_factory=lambda: [256, 256, 256])
+    teacher_hidden_dims: list = field(default_factory=lambda: [256, 256, 256])
+    activation: str = "elu"
+
+
+@dataclass
+class RslRlDistillationStudentTeacherRecurrentCfg(RslRlDistillationStudentTeacherCfg):
+    """rsl_rl's StudentTeacherRecurrent (h12env.distill.StudentTeacherRecurrent): a memory in front of the student, and
+    in front of the teacher when the teacher is a recurrent PPO policy."""
+    class_name: str = "StudentTeacherRecurrent"
+    rnn_type: str = "lstm"
+    rnn_hidden_dim: int = 256
+    rnn_num_layers: int = 1
+    teacher_recurrent: bool = False
+
+
+@dataclass
+class RslRlDistillationAlgorithmCfg:
+    """rsl_rl's Distillation (h12env.distill.Distillation)."""
+    class_name: str = "Distillation"
+    num_learning_epochs: int = 1
+    learning_rate: float = 1.0e-3
+    gradient_length: int = 15
+    loss_type: str = "mse"
+    # h12env.distill extension: a recurrent student's chunks on the h12learn_lstm_seq_* kernels (None:
+    # H12_RNN_UPDATE_FUSED)
+    fused_rnn_update: bool | None = None
+
+
+@dataclass
 class RslRlOnPolicyRunnerCfg:
     seed: int = 42
     device: str = "cuda:0"
     num_steps_per_env: int = 24
     max_iterations: int = 1500
     empirical_normalization: bool = False
-    policy: RslRlPpoActorCriticCfg = field(default_factory=RslRlPpoActorCriticCfg)
-    algorithm: RslRlPpoAlgorithmCfg = field(default_factory=RslRlPpoAlgorithmCfg)
+    policy: "RslRlPpoActorCriticCfg | RslRlDistillationStudentTeacherCfg" = field(default_factory=RslRlPpoActorCriticCfg)
+    algorithm: "RslRlPpoAlgorithmCfg | RslRlDistillationAlgorithmCfg" = field(default_factory=RslRlPpoAlgorithmCfg)
     clip_actions: float | None = None
     save_interval: int = 50
     experiment_name: str = "default"
@@ -182,5 +218,7 @@ def export_policy_as_onnx(policy, normalizer, path: str, filename="policy.onnx",
     return f(policy, normalizer, path, filename, verbose)
 
 
-__all__ = ["RslRlOnPolicyRunnerCfg", "RslRlPpoActorCriticCfg", "RslRlPpoAlgorithmCfg", "RslRlSymmetryCfg",
-           "RslRlVecEnvWrapper", "export_policy_as_jit", "export_policy_as_onnx"]
+__all__ = ["RslRlDistillationAlgorithmCfg", "RslRlDistillationStudentTeacherCfg",
+           "RslRlDistillationStudentTeacherRecurrentCfg", "RslRlOnPolicyRunnerCfg", "RslRlPpoActorCriticCfg",
+           "RslRlPpoAlgorithmCfg", "RslRlSymmetryCfg", "RslRlVecEnvWrapper", "export_policy_as_jit",
+           "export_policy_as_onnx"]

@@ -1,3 +1,4 @@
+from h12env.distill import Distillation
 from h12env.ppo import PPO
 
-__all__ = ["PPO"]
+__all__ = ["PPO", "Distillation"]

@@ -6200,6 +6200,25 @@ int h12env_cat_inline(const h12env* hh) {
   return h && h->cat_inline ? 1 : 0;
 }
 
+int h12env_cat_snapshot(h12env* hh, float* rows, float* running, uint32_t* still_mask, int32_t* still_list,
+                        int32_t* meta, float* max_p, void* stream) {
+  Handle* h = (Handle*)hh;
+  if (!h) return set_err(H12_E_ARG, "null handle");
+  if (!h->P.cat) return set_err(H12_E_STATE, "constraints are off in this env's config");
+  const KParams& P = h->P;
+  const size_t n = (size_t)h->W.n, nb = (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  hipStream_t st = (hipStream_t)stream;
+  if (rows) HIP_TRY(hipMemcpyAsync(rows, P.cscr, sizeof(float) * CAT_ROWS * n, hipMemcpyDefault, st));
+  if (running) HIP_TRY(hipMemcpyAsync(running, P.crun, sizeof(float) * 2 * H12_NCSTR_COLS, hipMemcpyDefault, st));
+  if (still_mask)  // (cat_cstill's section of the meta block)
+    HIP_TRY(hipMemcpyAsync(still_mask, P.cmeta + CAT_META_INTS, sizeof(uint32_t) * nb, hipMemcpyDefault, st));
+  if (still_list) HIP_TRY(hipMemcpyAsync(still_list, P.clist, sizeof(int32_t) * n, hipMemcpyDefault, st));
+  if (meta) HIP_TRY(hipMemcpyAsync(meta, P.cmeta, sizeof(int32_t) * 2, hipMemcpyDefault, st));
+  if (max_p)
+    for (int t = 0; t < H12_NCSTR; ++t) max_p[t] = P.cmaxp[t];
+  return 0;
+}
+
 int h12env_obs_fused(const h12env* hh) {
   const Handle* h = (const Handle*)hh;
   return h && h->fuse ? 1 : 0;

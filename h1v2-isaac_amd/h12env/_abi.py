@@ -284,6 +284,9 @@ def load_library(path: str | os.PathLike | None = None):
     if hasattr(lib, "h12env_cat_inline"):  # (a round-5 library, loaded as an A/B baseline, lacks it)
         lib.h12env_cat_inline.argtypes = [vp]
         lib.h12env_cat_inline.restype = C.c_int
+    if hasattr(lib, "h12env_cat_snapshot"):  # (an older library, loaded as an A/B baseline, lacks it)
+        lib.h12env_cat_snapshot.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), vp]
+        lib.h12env_cat_snapshot.restype = C.c_int
     lib.h12env_observe.argtypes = [vp, vp, vp, vp, vp]
     lib.h12env_observe.restype = C.c_int
     lib.h12env_set_terrain.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, vp, C.c_int, C.c_int]
@@ -360,6 +363,7 @@ EXPORTED_SYMBOLS = [
     "h12env_last_error", "h12env_abi_version", "h12env_sizeof_struct", "h12env_kernel_cost",
     "h12env_set_kernel_timing", "h12env_kernel_times", "h12env_set_terrain", "h12env_obs_dim",
     "h12env_set_reward_weights", "h12env_set_constraint_max_p", "h12env_eval_terms", "h12env_eval_self_contacts",
+    "h12env_cat_snapshot",
     "h12env_rollout_layout", "h12env_rollout_decode", "h12env_fence_create", "h12env_fence_destroy",
     "h12env_fence_signal", "h12env_fence_wait", "h12env_step_lds", "h12env_check",
     "h12env_monitor_layout", "h12env_step_physics_monitored", "h12env_monitor_reduce",

@@ -872,6 +872,28 @@ class H12VelocityEnv:
         separate probability kernel after it."""
         return hasattr(self._lib, "h12env_cat_inline") and bool(self._lib.h12env_cat_inline(self._h))
 
+    def cat_snapshot(self) -> dict:
+        """Parity hook (h12env_cat_snapshot): what the last step() left of CaT's cross-env pass, as host numpy arrays
+        -- rows (NCSTR_COLS + 2, N) f32: the raw columns, the no_move flag, the pre-reset episode length; running
+        (2, NCSTR_COLS) f32: running maxima and their reciprocals; still_mask (ceil(N / 32),) u32; still_list (N,) i32
+        (entries [0, m) valid, two-kernel path only); m; initialised; max_p (NCSTR,) f32.  Synchronises the stream."""
+        n = self.num_envs
+        dev = self.device
+        rows = torch.empty(_abi.NCSTR_COLS + 2, n, device=dev)
+        run = torch.empty(2, _abi.NCSTR_COLS, device=dev)
+        mask = torch.empty((n + 31) // 32, dtype=torch.int32, device=dev)
+        lst = torch.empty(n, dtype=torch.int32, device=dev)
+        meta = torch.empty(2, dtype=torch.int32, device=dev)
+        max_p = (C.c_float * NCSTR)()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(self._lib, self._lib.h12env_cat_snapshot(self._h, p(rows), p(run), p(mask), p(lst), p(meta), max_p,
+                                                       self._stream()), "h12env_cat_snapshot")
+        meta = meta.cpu().numpy()
+        return {"rows": rows.cpu().numpy(), "running": run.cpu().numpy(),
+                "still_mask": mask.cpu().numpy().view("uint32"), "still_list": lst.cpu().numpy(),
+                "m": int(meta[0]), "initialised": bool(meta[1]),
+                "max_p": torch.tensor(list(max_p), dtype=torch.float32).numpy()}
+
     def kernel_cost(self, kernel: int):
         """(compulsory HBM bytes, counted FLOPs) per env of kernel 0 (env step) or 1 (obs assembly, or the log fold
         per step on the fused path)."""

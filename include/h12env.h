@@ -443,6 +443,23 @@ int h12env_eval_terms(h12env* h, const float* tau, const float* jacc, const floa
  * right), body (knee, foot): moment xyz, force xyz in body coordinates.  Replaces nothing in the reference (its
  * self-collisions live inside PhysX, ArticulationCfg enabled_self_collisions, A/robots/h12.py:32). */
 int h12env_eval_self_contacts(h12env* env, float* out, void* stream);
+
+/* Parity hook (tests only; additive to ABI 9): what the last h12env_step of a CaT handle left of the cross-env pass
+ * (ConstraintManager.compute's running maxima and constraints.no_move's row remap, constraint_manager.py:42-78,
+ * constraints.py:202-238).  Copies only (hipMemcpyAsync on `stream`, so ordered after the step on the same stream; the
+ * caller synchronises before reading), launches nothing, changes nothing.  Any output may be NULL; the first five may
+ * be device or host pointers, max_p is host memory.
+ *   rows        [H12_NCSTR_COLS + 2][N] f32  the step's raw columns, the no_move flag, the pre-reset episode length
+ *   running     [2][H12_NCSTR_COLS]     f32  running maxima, then their reciprocals
+ *   still_mask  [ceil(N / 32)]          u32  the 32-env blocks' still-env masks (bit j: env 32 b + j)
+ *   still_list  [N]                     i32  the ascending still list (entries [0, m) valid; two-kernel path only)
+ *   meta        [2]                     i32  m, "running maxima initialised"
+ *   max_p       [H12_NCSTR]             f32  the per-term max_p as the handle holds it at the call -- a kernel
+ *                                            argument kept on the host, written before the function returns; it is
+ *                                            what the last step used unless h12env_set_constraint_max_p ran since
+ * H12_E_STATE on a handle without CaT. */
+int h12env_cat_snapshot(h12env* h, float* rows, float* running, uint32_t* still_mask, int32_t* still_list,
+                        int32_t* meta, float* max_p, void* stream);
 /* ---- Rollout records (ABI 8; BASELINE config C4: the rollout buffer all-gathered over xGMI for PPO).
  * rsl_rl's RolloutStorage keeps (T, N, 450) observations per iteration (T = num_steps_per_env 24,
  * C12/agents/rsl_rl_ppo_cfg.py:12).  A 450-float row is 10 frames of 45 floats, nine of them already in the previous

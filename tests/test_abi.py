@@ -29,6 +29,16 @@ def test_library_exports_header_symbols():
         assert hasattr(lib, n), n
 
 
+def test_cat_snapshot_hook_is_exported_and_checks_its_handle():
+    """h12env_cat_snapshot (the CaT parity hook): declared, exported, bound, and a null handle is an argument error
+    before any HIP call."""
+    assert "h12env_cat_snapshot" in header_functions() and "h12env_cat_snapshot" in EXPORTED_SYMBOLS
+    lib = load_library()
+    assert lib.h12env_cat_snapshot.restype is C.c_int and len(lib.h12env_cat_snapshot.argtypes) == 8
+    assert lib.h12env_cat_snapshot(None, None, None, None, None, None, None, None) == -1
+    assert b"null handle" in lib.h12env_last_error()
+
+
 def test_struct_sizes_match():
     lib = load_library()
     for i, st in enumerate((H12Model, H12Config, H12StepOut)):

@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 import oracle as O
+from cat_ref import cat_pass_numpy
 from h12env._abi import CONSTRAINT_TERMS, NCSTR, NREW, REWARD_FUNCS
 from h12env._abi import F as FIELDS
 from h12env.cfg import ConstraintPTerm, H12CaTEnvCfg, H12RslEnvCfg
 from h12env.startup import apply_to_arrays, startup_state
-
-COL0 = [0, 1, 13, 25, 37, 39, 51, 52, 53, 54, 56]
 
 
 def test_cat_cfg_maps_onto_the_kernel():
@@ -62,28 +61,6 @@ def cat_oracle(model, n, seed=0):
 def field(F, k):
     o, cnt = FIELDS[k]
     return F[o:o + cnt]
-
-
-def cat_pass_numpy(cs, run_prev, max_p, tau=float(np.float32(0.95)), min_p=0.0, mask=(1 << NCSTR) - 1):
-    """constraint_manager.py:42-78 (CaT.add / get_probs) + no_move's row remap (constraints.py:202-238)."""
-    n = cs.shape[1]
-    still = np.nonzero(cs[56] != 0)[0]
-    rows = cs[:56].copy()
-    nm = slice(COL0[5], COL0[6])
-    if len(still):
-        rows[nm] = cs[nm][:, still[np.arange(n) % len(still)]]
-    else:
-        rows[nm] = 0.0
-    cmax = np.maximum(rows.max(axis=1), 1e-6)
-    run = cmax if run_prev is None else tau * run_prev + (1 - tau) * cmax
-    pt = np.zeros((NCSTR, n))
-    for t in range(NCSTR):
-        if not (mask >> t) & 1:
-            continue
-        r = rows[COL0[t]:COL0[t + 1]]
-        p = np.where(r > 0, min_p + np.clip(r / run[COL0[t]:COL0[t + 1], None], 0, 1) * (max_p[t] - min_p), 0.0)
-        pt[t] = p.max(axis=0)
-    return run, pt, pt.max(axis=0)
 
 
 def test_cat_pass_matches_numpy_restatement(model):

@@ -13,6 +13,8 @@
 // The block's rows are staged in LDS as they lie in the output ([env][W], no padding) and leave as ONE contiguous span
 // of nb * W floats in 16-byte stores (EPB * W * 4 bytes per full block, a multiple of 16 for both layouts); the last
 // (nb * W) % 4 floats of a ragged last block leave in scalar stores.
+// h12priv_observe_terms (the rnd_state group) launches priv_terms_kernel: the same block body
+// (priv_rows), whose rows then leave column run by column run into the compacted [n][W'] output.
 // Device code is compiled with -ffinite-math-only and a diverged base can be non-finite: whatever becomes a heightfield
 // index is taken from values whose bit patterns were checked first (sane_bits), and the indices are clamped once more
 // with integer operations.  Everything else is arithmetic into fixed addresses.
@@ -56,6 +58,10 @@ struct PrivArgs {
   int env_mu, env_mass;
   float scan_off, scan_clip;
   float scale[H12PRIV_NTERMS];
+  // h12priv_observe_terms only: the compacted row's width, whether the scan is among the terms, and the runs of
+  // consecutive columns of the full row that make it up (adjacent terms merged)
+  int Wout, scan_on, nseg;
+  struct { int src, dst, w; } seg[H12PRIV_NTERMS];
 };
 
 // |x| <= 1e6 on the bit pattern: false for NaN, +-inf and magnitudes whose products below could overflow
@@ -113,9 +119,10 @@ __device__ __forceinline__ void scan_pose(const PrivArgs& A, int e, float* p) {
   }
 }
 
-template <int PRIV_EPB, bool TERRAIN>
-__global__ __launch_bounds__(PRIV_BLOCK) void priv_obs_kernel(PrivArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float rows[];  // [PRIV_EPB][W]
+// The block's work, shared by the two kernels below.  MASKED (h12priv_observe_terms): the rows are built in LDS by the
+// same code, and only the columns of A.seg leave.
+template <int PRIV_EPB, bool TERRAIN, bool MASKED>
+__device__ __forceinline__ void priv_rows(const PrivArgs& A, float* rows /* LDS [PRIV_EPB][W] */) {
   const int W = A.W, n = A.n, t = threadIdx.x;
   const int e0 = blockIdx.x * PRIV_EPB;
   const int nb = n - e0 < PRIV_EPB ? n - e0 : PRIV_EPB;
@@ -197,7 +204,7 @@ __global__ __launch_bounds__(PRIV_BLOCK) void priv_obs_kernel(PrivArgs A) {
         rows[el * W + COL_JOINT + j] = (term == 0 ? v[i] - q0_of(j) : v[i]) * (term == 0 ? s0 : (term == 1 ? s1 : s2));
     }
   }
-  if (TERRAIN) {
+  if (TERRAIN && (!MASKED || A.scan_on)) {
     static_assert(!TERRAIN || PRIV_BLOCK == PRIV_EPB * SCAN_TPE, "SCAN_TPE threads per env");
     static_assert((PRIV_EPB & (PRIV_EPB - 1)) == 0 && PRIV_EPB <= 64, "envs per block");
     const int el = t / SCAN_TPE, r0 = t - el * SCAN_TPE;
@@ -219,6 +226,16 @@ __global__ __launch_bounds__(PRIV_BLOCK) void priv_obs_kernel(PrivArgs A) {
     }
   }
   __syncthreads();
+  if (MASKED) {  // run by run: item i of a run is (env i / w, column i % w); e0 + el < n and dst + c < Wout
+    for (int k = 0; k < A.nseg; ++k) {
+      const int w = A.seg[k].w, src = A.seg[k].src, dstc = A.seg[k].dst;
+      for (int i = t; i < nb * w; i += PRIV_BLOCK) {
+        const int el = i / w, c = i - el * w;
+        A.out[(size_t)(e0 + el) * A.Wout + dstc + c] = rows[el * W + src + c];
+      }
+    }
+    return;
+  }
   const int total = nb * W;
   float* dst = A.out + (size_t)e0 * W;
   int done = 0;
@@ -229,6 +246,18 @@ __global__ __launch_bounds__(PRIV_BLOCK) void priv_obs_kernel(PrivArgs A) {
     done = nv << 2;
   }
   for (int i = done + t; i < total; i += PRIV_BLOCK) dst[i] = rows[i];
+}
+
+template <int PRIV_EPB, bool TERRAIN>
+__global__ __launch_bounds__(PRIV_BLOCK) void priv_obs_kernel(PrivArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float rows[];  // [PRIV_EPB][W]
+  priv_rows<PRIV_EPB, TERRAIN, false>(A, rows);
+}
+
+template <int PRIV_EPB, bool TERRAIN>
+__global__ __launch_bounds__(PRIV_BLOCK) void priv_terms_kernel(PrivArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float rows[];  // [PRIV_EPB][W]
+  priv_rows<PRIV_EPB, TERRAIN, true>(A, rows);
 }
 
 thread_local char g_err[256] = "";
@@ -267,8 +296,13 @@ int h12priv_layout(int terrain, int32_t* width, int32_t table[H12PRIV_NTERMS][3]
   return H12PRIV_OK;
 }
 
-int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force, float* out,
-                    void* stream) {
+}  // extern "C"
+
+namespace {
+
+// the argument checks of both launches and the kernel arguments they share
+int fill_args(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force, float* out,
+              PrivArgs& A) {
   if (!workspace) return fail(H12PRIV_E_ARG, "workspace: null");
   if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(H12PRIV_E_ARG, "workspace: not 4-byte aligned");
   if (n < 1) return fail(H12PRIV_E_ARG, "n: %d (>= 1)", n);
@@ -291,7 +325,6 @@ int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, con
   for (int t = 0; t < H12PRIV_NTERMS; ++t)
     if (!fin(cfg->scale[t])) return fail(H12PRIV_E_ARG, "cfg.scale[%d]: not finite", t);
 
-  PrivArgs A;
   memset(&A, 0, sizeof A);
   A.F = static_cast<const float*>(workspace);
   A.I = reinterpret_cast<const int32_t*>(A.F + (size_t)H12_NF_FLOAT * n);
@@ -308,6 +341,58 @@ int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, con
   A.mus = cfg->mu_static; A.mud = cfg->mu_dynamic;
   A.env_mu = cfg->per_env_friction != 0; A.env_mass = cfg->per_env_mass != 0;
   for (int t = 0; t < H12PRIV_NTERMS; ++t) A.scale[t] = cfg->scale[t];
+  return H12PRIV_OK;
+}
+
+// the runs of a term mask: H12PRIV_E_ARG for a mask that names no term, a term past the table, or height_scan
+// without a heightfield
+int mask_runs(int terrain, uint32_t mask, PrivArgs* A, int32_t* width, int32_t table[H12PRIV_NTERMS][3],
+              int32_t* n_terms) {
+  if (mask == 0) return fail(H12PRIV_E_ARG, "term_mask: 0 (names no term)");
+  if (mask >> H12PRIV_NTERMS)
+    return fail(H12PRIV_E_ARG, "term_mask: 0x%x names a term past the table (%d terms)", mask, H12PRIV_NTERMS);
+  if (((mask >> H12PRIV_T_HEIGHT_SCAN) & 1u) && !terrain)
+    return fail(H12PRIV_E_ARG, "term_mask: height_scan on a plane task (no heightfield)");
+  int src = 0, dst = 0, rows = 0, nseg = 0;
+  for (int t = 0; t < H12PRIV_NTERMS; ++t) {
+    if (t == H12PRIV_T_HEIGHT_SCAN && !terrain) continue;
+    const int w = TERM_WIDTH[t];
+    if ((mask >> t) & 1u) {
+      if (table) { table[rows][0] = t; table[rows][1] = dst; table[rows][2] = w; }
+      if (A) {
+        if (nseg && A->seg[nseg - 1].src + A->seg[nseg - 1].w == src) {
+          A->seg[nseg - 1].w += w;
+        } else {
+          A->seg[nseg].src = src; A->seg[nseg].dst = dst; A->seg[nseg].w = w;
+          ++nseg;
+        }
+      }
+      dst += w;
+      ++rows;
+    }
+    src += w;
+  }
+  if (A) { A->nseg = nseg; A->Wout = dst; A->scan_on = (mask >> H12PRIV_T_HEIGHT_SCAN) & 1u; }
+  if (width) *width = dst;
+  if (n_terms) *n_terms = rows;
+  return H12PRIV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int h12priv_layout_terms(int terrain, uint32_t term_mask, int32_t* width, int32_t table[H12PRIV_NTERMS][3],
+                         int32_t* n_terms) {
+  if (terrain != 0 && terrain != 1) return fail(H12PRIV_E_ARG, "terrain: %d (0 | 1)", terrain);
+  return mask_runs(terrain, term_mask, nullptr, width, table, n_terms);
+}
+
+int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force, float* out,
+                    void* stream) {
+  PrivArgs A;
+  const int rc = fill_args(workspace, n, cfg, foot_force, out, A);
+  if (rc != H12PRIV_OK) return rc;
   const int epb = A.terrain ? EPB_TERRAIN : EPB_PLANE;
   const int blocks = (n + epb - 1) / epb;
   const size_t lds = (size_t)epb * A.W * sizeof(float);
@@ -316,6 +401,25 @@ int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, con
     hipLaunchKernelGGL((priv_obs_kernel<EPB_TERRAIN, true>), dim3(blocks), dim3(PRIV_BLOCK), lds, s, A);
   else
     hipLaunchKernelGGL((priv_obs_kernel<EPB_PLANE, false>), dim3(blocks), dim3(PRIV_BLOCK), lds, s, A);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(H12PRIV_E_HIP, "launch: %s", hipGetErrorString(err));
+  return H12PRIV_OK;
+}
+
+int h12priv_observe_terms(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force,
+                          uint32_t term_mask, float* out, void* stream) {
+  PrivArgs A;
+  int rc = fill_args(workspace, n, cfg, foot_force, out, A);
+  if (rc == H12PRIV_OK) rc = mask_runs(cfg->terrain, term_mask, &A, nullptr, nullptr, nullptr);
+  if (rc != H12PRIV_OK) return rc;
+  const int epb = A.terrain ? EPB_TERRAIN : EPB_PLANE;
+  const int blocks = (n + epb - 1) / epb;
+  const size_t lds = (size_t)epb * A.W * sizeof(float);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (A.terrain)
+    hipLaunchKernelGGL((priv_terms_kernel<EPB_TERRAIN, true>), dim3(blocks), dim3(PRIV_BLOCK), lds, s, A);
+  else
+    hipLaunchKernelGGL((priv_terms_kernel<EPB_PLANE, false>), dim3(blocks), dim3(PRIV_BLOCK), lds, s, A);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(H12PRIV_E_HIP, "launch: %s", hipGetErrorString(err));
   return H12PRIV_OK;

@@ -20,7 +20,7 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_cleanrl_head", "h12learn_lstm_max_hidden", "h12learn_lstm_packed_bytes",
                  "h12learn_lstm_pack", "h12learn_lstm_step", "h12learn_lstm_seq_packed_bytes",
                  "h12learn_lstm_seq_pack", "h12learn_lstm_seq_forward", "h12learn_lstm_seq_backward",
-                 "h12learn_last_error"]
+                 "h12learn_rnd_reward", "h12learn_rnd_finish", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -111,6 +111,14 @@ class CleanRlHeadArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class RndFinishArgs(C.Structure):
+    """h12learn_rnd_finish_args"""
+    _fields_ = [("n", C.c_longlong), ("normalize", C.c_int), ("gamma", C.c_float), ("until", C.c_longlong),
+                ("err", C.c_void_p), ("ext_reward", C.c_void_p), ("weight", C.c_void_p), ("avg", C.c_void_p),
+                ("mean", C.c_void_p), ("var", C.c_void_p), ("std", C.c_void_p), ("count", C.c_void_p),
+                ("first", C.c_void_p), ("intrinsic", C.c_void_p), ("total", C.c_void_p)]
+
+
 _bound = None
 
 
@@ -188,6 +196,10 @@ def learn_library():
     lib.h12learn_lstm_seq_forward.restype = C.c_int
     lib.h12learn_lstm_seq_backward.argtypes = [C.POINTER(LstmSeqDesc), vp, C.POINTER(LstmSeqGradIo), vp]
     lib.h12learn_lstm_seq_backward.restype = C.c_int
+    lib.h12learn_rnd_reward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.c_longlong, vp, vp, C.POINTER(C.c_void_p), vp]
+    lib.h12learn_rnd_reward.restype = C.c_int
+    lib.h12learn_rnd_finish.argtypes = [C.POINTER(RndFinishArgs), vp]
+    lib.h12learn_rnd_finish.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -780,3 +792,38 @@ def cleanrl_head(mean: torch.Tensor, value: torch.Tensor, logstd: torch.Tensor, 
     return outputs
 
 
+
+
+# ---- Random Network Distillation's reward step (csrc/h12_rnd.hip)
+def rnd_reward(desc: MlpDesc, packed: torch.Tensor, x: torch.Tensor, err: torch.Tensor | None = None,
+               xn: torch.Tensor | None = None, emb: bool = False):
+    """One launch: err [n] = the row norm of target - predictor on the normalised ``x`` [n][d_in] (desc: nets[0] the
+    predictor, nets[1] the target).  ``xn`` ([n][d_in] or None) receives the normalised rows.  Returns err, or with
+    ``emb`` (a test hook) (err, predictor embedding, target embedding)."""
+    lib = learn_library()
+    _f32(packed, "packed"), _f32(x, "x")
+    if x.dim() != 2 or x.shape[1] != desc.d_in or x.shape[0] < 1:
+        raise ValueError(f"rnd_reward: x {tuple(x.shape)} is not (n >= 1, {desc.d_in})")
+    n = x.shape[0]
+    if err is None:
+        err = torch.empty(n, dtype=torch.float32, device=x.device)
+    elif _f32(err, "err").shape != (n,):
+        raise ValueError(f"rnd_reward: err must be ({n},)")
+    if xn is not None and _f32(xn, "xn").shape != x.shape:
+        raise ValueError("rnd_reward: xn must have x's shape")
+    embs, ptrs = None, None
+    if emb:
+        w = desc.nets[0].dims[desc.nets[0].n_layers]
+        embs = tuple(torch.empty((n, w), dtype=torch.float32, device=x.device) for _ in range(2))
+        ptrs = (C.c_void_p * 2)(*[e.data_ptr() for e in embs])
+    _check(lib, lib.h12learn_rnd_reward(C.byref(desc), packed.data_ptr(), x.data_ptr(), n, err.data_ptr(),
+                                        None if xn is None else xn.data_ptr(), ptrs, _stream(x.device)),
+           "h12learn_rnd_reward")
+    return (err, *embs) if emb else err
+
+
+def rnd_finish(args: RndFinishArgs, device):
+    """One launch of one block: reward normaliser, weight and the sum with the env's reward (h12learn_rnd_finish).  The
+    caller fills ``args`` with the data pointers of tensors it keeps alive."""
+    lib = learn_library()
+    _check(lib, lib.h12learn_rnd_finish(C.byref(args), _stream(device)), "h12learn_rnd_finish")

@@ -274,6 +274,33 @@ def enable_student_observations(env_cfg, history_length: int | None = None):
         obs.student.history_length = int(history_length)
 
 
+RND_STATE_TERMS = ("base_lin_vel", "base_ang_vel", "projected_gravity", "joint_pos", "joint_vel", "base_height",
+                   "feet_contact")
+
+
+@dataclass
+class RndStateObsCfg:
+    """The observation group Random Network Distillation reads as extras["observations"]["rnd_state"] (h12env.rnd,
+    DESIGN.md section 7t): one noise-free row per env, no history -- any subset of the privileged row's terms
+    (h12env.priv.TERMS) in that row's order and with its scales.  The default is 36 floats wide.  height_scan needs a
+    heightfield task."""
+    enable_corruption: bool = False
+    concatenate_terms: bool = True
+    history_length: int = 0
+    terms: tuple = RND_STATE_TERMS
+
+
+def enable_rnd_state(env_cfg, terms=None):
+    """The scripts' --rnd: switch the env cfg's rnd_state observation group on (defaults, or the given terms)."""
+    obs = getattr(env_cfg, "observations", None)
+    if obs is None or "rnd_state" not in getattr(obs, "__dataclass_fields__", {}):
+        raise ValueError("--rnd: this task's env cfg has no rnd_state observation group")
+    if obs.rnd_state is None:
+        obs.rnd_state = RndStateObsCfg()
+    if terms is not None:
+        obs.rnd_state.terms = tuple(terms)
+
+
 @dataclass
 class ObservationsCfg:
     policy: PolicyObsCfg = field(default_factory=PolicyObsCfg)
@@ -281,6 +308,8 @@ class ObservationsCfg:
     critic: CriticObsCfg | None = field(default=None, metadata={"omit_if_none": True})
     # None: no student group (nothing is launched for it); left out of the cfg dumps while it is None
     student: StudentObsCfg | None = field(default=None, metadata={"omit_if_none": True})
+    # None: no rnd_state group (nothing is launched for it); left out of the cfg dumps while it is None
+    rnd_state: RndStateObsCfg | None = field(default=None, metadata={"omit_if_none": True})
 
 
 @dataclass

@@ -553,6 +553,9 @@ class DistillationRunner(OnPolicyRunner):
         if self.alg_cfg.get("symmetry_cfg") is not None:
             raise ValueError("symmetry_cfg is not supported with Distillation (the student copies the teacher's action; "
                              "train the teacher with symmetry instead)")
+        if self.alg_cfg.get("rnd_cfg") is not None:
+            raise ValueError("rnd_cfg is not supported with Distillation (there is no reward to add an exploration "
+                             "bonus to)")
         class_name = self.policy_cfg.pop("class_name")
         self.empirical_normalization = bool(train_cfg.get("empirical_normalization", False))
         if self.empirical_normalization and class_name == "StudentTeacherRecurrent":

@@ -9,6 +9,7 @@ in packages/biped_tasks/biped_tasks/utils/cat/cat_env.py:95-193):
   num_envs, device, step_dt, physics_dt, max_episode_length(_s), episode_length_buf (writable),
   cfg, observation_manager.group_obs_dim, action_manager.total_action_dim, unwrapped, close()
 
+With cfg.observations.rnd_state set they hold "rnd_state" (a subset of the privileged row's terms, for h12env.rnd).
 With cfg.observations.critic set, the obs dicts also hold "critic": the privileged rows of h12env.priv (one more
 launch per step, behind the env's on the same stream).  With cfg.observations.student set they hold "student": the
 deployable rows of h12env.student (one more launch per step() / reset(); observe() / compute() return them unchanged).
@@ -155,6 +156,10 @@ class _ObservationManager:
             self.group_obs_dim["critic"] = (env.critic_obs_dim,)
             self.group_obs_concatenate["critic"] = True
             self.active_terms["critic"] = term_names(env.terrain is not None)
+        if env._rnd is not None:  # the rnd_state group (h12env.rnd)
+            self.group_obs_dim["rnd_state"] = (env.rnd_state_dim,)
+            self.group_obs_concatenate["rnd_state"] = True
+            self.active_terms["rnd_state"] = list(env._rnd_terms)
         if env._stu is not None:  # the deployable group (h12env.student)
             from .student import TERMS
 
@@ -324,6 +329,7 @@ class H12VelocityEnv:
         self.terrain = None
         self._apply_startup()
         self._init_critic()
+        self._init_rnd_state()
         self._init_student()
         if self.terrain is not None:
             origins = self._field("ORIGIN").T  # moved in-kernel by the terrain curriculum
@@ -377,6 +383,42 @@ class H12VelocityEnv:
         if rc:
             check_priv(lib, rc, "h12priv_observe")
 
+    def _init_rnd_state(self):
+        """The rnd_state observation group (cfg.observations.rnd_state, h12env.priv's masked rows): its config struct,
+        term mask and the two row buffers, swapped with the policy's.  None when the group is off."""
+        self._rnd = None
+        self.rnd_state_dim = None
+        rc = getattr(self.cfg.observations, "rnd_state", None)
+        if rc is None:
+            return
+        from . import priv
+
+        if rc.history_length not in (0, 1, None):
+            raise ValueError("the rnd_state observation has no history (history_length 0)")
+        if not rc.concatenate_terms:
+            raise ValueError("the rnd_state observation is one concatenated row (concatenate_terms=True)")
+        mask = priv.term_mask(rc.terms)
+        self._rnd_terms = [t for t in priv.TERMS if t in set(rc.terms)]
+        if list(rc.terms) != self._rnd_terms:
+            raise ValueError(f"rnd_state terms {list(rc.terms)} must be distinct and in the privileged row's order "
+                             f"{self._rnd_terms}")
+        if "height_scan" in self._rnd_terms and self.terrain is None:
+            raise ValueError("rnd_state: height_scan needs a heightfield task")
+        lib = priv.priv_library()
+        pc = priv.priv_config(self)
+        self.rnd_state_dim, _ = priv.layout_terms(bool(pc.terrain), mask)
+        self._rnd_rows_buf = [torch.zeros(self.num_envs, self.rnd_state_dim, device=self.device) for _ in range(2)]
+        self._rnd = (lib, pc, C.byref(pc), priv.check, mask)
+
+    def _rnd_rows(self):
+        """h12priv_observe_terms of the workspace as it stands into the current rnd_state buffer: one launch behind the
+        env's kernels on the same stream, no host sync."""
+        lib, _, ref, check_priv, mask = self._rnd
+        rc = lib.h12priv_observe_terms(self._state.data_ptr(), self.num_envs, ref, self.foot_contact_force.data_ptr(),
+                                       mask, self._rnd_rows_buf[self._k].data_ptr(), _raw_stream(self._dev_index))
+        if rc:
+            check_priv(lib, rc, "h12priv_observe_terms")
+
     def _init_student(self):
         """The deployable observation group (cfg.observations.student, h12env.student): its config struct and the two
         row buffers the history lives in.  They swap on every push (step() / reset()) and only then, so they have an
@@ -413,12 +455,15 @@ class H12VelocityEnv:
     def _groups(self, policy, copy):
         """The observation dict: the policy rows and, with the privileged / deployable groups on, the current critic /
         student rows."""
-        if self._priv is None and self._stu is None:
+        if self._priv is None and self._stu is None and self._rnd is None:
             return {"policy": policy}
         out = {"policy": policy}
         if self._priv is not None:
             c = self._crit[self._k]
             out["critic"] = c.clone() if copy else c
+        if self._rnd is not None:
+            c = self._rnd_rows_buf[self._k]
+            out["rnd_state"] = c.clone() if copy else c
         if self._stu is not None:
             r = self._stu_rows[self._sk]
             out["student"] = r.clone() if copy else r
@@ -491,6 +536,8 @@ class H12VelocityEnv:
                 groups["critic"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.critic_obs_dim,))
             if self._stu is not None:
                 groups["student"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.student_obs_dim,))
+            if self._rnd is not None:
+                groups["rnd_state"] = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(self.rnd_state_dim,))
             self.single_observation_space = gym.spaces.Dict(groups)
             self.single_action_space = gym.spaces.Box(low=-np.inf, high=np.inf, shape=(NJ,))
             self.observation_space = gym.vector.utils.batch_space(self.single_observation_space, self.num_envs)
@@ -506,6 +553,9 @@ class H12VelocityEnv:
             if self._stu is not None:
                 self.single_observation_space["student"] = (self.student_obs_dim,)
                 self.observation_space["student"] = (self.num_envs, self.student_obs_dim)
+            if self._rnd is not None:
+                self.single_observation_space["rnd_state"] = (self.rnd_state_dim,)
+                self.observation_space["rnd_state"] = (self.num_envs, self.rnd_state_dim)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -616,6 +666,8 @@ class H12VelocityEnv:
         self.extras = {}
         if self._priv is not None:
             self._critic_rows()
+        if self._rnd is not None:
+            self._rnd_rows()
         if self._stu is not None:
             self._stu_resets += 1
             self._student_push(-self._stu_resets, fill_all=mask is None, fill_mask=mask)
@@ -672,11 +724,13 @@ class H12VelocityEnv:
         self._live_logs[self.common_step_counter] = weakref.ref(log)
         self.extras = {"log": log, "time_outs": self.reset_time_outs}
         obs_out = obs.clone() if self.obs_copy else obs
-        if self._priv is None and self._stu is None:
+        if self._priv is None and self._stu is None and self._rnd is None:
             obs_dict = {"policy": obs_out}
         else:
             if self._priv is not None:
                 self._critic_rows()
+            if self._rnd is not None:
+                self._rnd_rows()
             if self._stu is not None:
                 self._student_push(self.common_step_counter)
             obs_dict = self._groups(obs_out, self.obs_copy)
@@ -697,6 +751,9 @@ class H12VelocityEnv:
             raise ValueError("bind_rollout with a critic observation group: the compact records carry no critic row")
         if self._stu is not None:
             raise ValueError("bind_rollout with a student observation group: the compact records carry no student row")
+        if self._rnd is not None:
+            raise ValueError("bind_rollout with an rnd_state observation group: the compact records carry no rnd_state "
+                             "row")
         if rec.n != self.num_envs or rec.history * 45 != self.obs_dim:
             raise ValueError("rollout recorder was built for another env shape")
         self._rollout_saved = (self.reward_buf, self.reset_terminated, self.reset_time_outs)
@@ -776,6 +833,8 @@ class H12VelocityEnv:
                                                   self._stream()), "h12env_observe")
         if self._priv is not None:
             self._critic_rows()
+        if self._rnd is not None:
+            self._rnd_rows()
         return self._groups(out, False)
 
     def get_observations(self):
@@ -790,6 +849,9 @@ class H12VelocityEnv:
         if self._priv is not None:  # the critic rows and the foot forces the next reset() / observe() reads
             snap["critic"] = [c.clone() for c in self._crit]
             snap["foot_force"] = self.foot_contact_force.clone()
+        if self._rnd is not None:  # the rnd_state rows and the foot forces, as for the critic group
+            snap["rnd_state"] = [c.clone() for c in self._rnd_rows_buf]
+            snap["foot_force"] = self.foot_contact_force.clone()
         if self._stu is not None:  # both row buffers (the history), which one is current, and the reset-noise counter
             snap["student"] = ([r.clone() for r in self._stu_rows], self._sk, self._stu_resets)
         return snap
@@ -802,6 +864,10 @@ class H12VelocityEnv:
         if self._priv is not None:
             for c, s in zip(self._crit, snap["critic"]):
                 c.copy_(s)
+            self.foot_contact_force.copy_(snap["foot_force"])
+        if self._rnd is not None:
+            for c, s_ in zip(self._rnd_rows_buf, snap["rnd_state"]):
+                c.copy_(s_)
             self.foot_contact_force.copy_(snap["foot_force"])
         if self._stu is not None:
             rows, self._sk, self._stu_resets = snap["student"]

@@ -301,7 +301,7 @@ class RolloutStorage:
     t = 0 and those only (rsl_rl keeps every step's).  PPO.process_env_step zeroes the state right after a done, so every
     trajectory that starts later than t = 0 starts from zeros, and recurrent_mini_batch_generator needs no more."""
 
-    def __init__(self, num_envs, num_steps, obs_dim, critic_obs_dim, num_actions, device):
+    def __init__(self, num_envs, num_steps, obs_dim, critic_obs_dim, num_actions, device, rnd_state_dim=None):
         T, N = num_steps, num_envs
         self.num_envs, self.num_steps, self.device = N, T, device
         z = lambda *s: torch.zeros(*s, device=device)  # noqa: E731
@@ -319,6 +319,8 @@ class RolloutStorage:
         }
         if critic_obs_dim is not None:
             self.t["privileged_observations"] = z(T, N, critic_obs_dim)
+        if rnd_state_dim is not None:  # Random Network Distillation: the normalised rnd_state rows
+            self.t["rnd_state"] = z(T, N, rnd_state_dim)
         self.step = 0
 
     def __getattr__(self, k):
@@ -327,7 +329,7 @@ class RolloutStorage:
             return t[k]
         raise AttributeError(k)
 
-    def add(self, obs, critic_obs, actions, rewards, dones, values, log_prob, mu, sigma):
+    def add(self, obs, critic_obs, actions, rewards, dones, values, log_prob, mu, sigma, rnd_state=None):
         if self.step >= self.num_steps:
             raise OverflowError("rollout buffer overflow; call clear() before adding new transitions")
         s = self.step
@@ -342,6 +344,8 @@ class RolloutStorage:
         t["actions_log_prob"][s].copy_(log_prob.view(-1, 1))
         t["mu"][s].copy_(mu)
         t["sigma"][s].copy_(sigma)
+        if rnd_state is not None:
+            t["rnd_state"][s].copy_(rnd_state)
         self.step += 1
 
     def clear(self):
@@ -488,7 +492,7 @@ class PPO:
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
                  symmetry_cfg: dict | None = None, fused_learner: bool | None = None, fused_loss: bool | None = None,
-                 fused_rnn_update: bool | None = None, **kwargs):
+                 fused_rnn_update: bool | None = None, rnd_cfg: dict | None = None, **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
@@ -602,11 +606,40 @@ class PPO:
                              "data_augmentation_func": resolve_func(s.get("data_augmentation_func")),
                              "_env": s.get("_env")}
         self._n_stats = 3 if self.symmetry is None else 4
+        # rsl_rl 2.3 rnd_cfg: Random Network Distillation (h12env.rnd).  None: nothing changes.  The cfg
+        # arrives resolved (num_states set, weight scaled by step_dt: rnd.resolve_rnd_cfg, the runner's part).
+        self.rnd = None
+        if rnd_cfg is not None:
+            self._init_rnd(dict(rnd_cfg), symmetry_cfg, fused)
+
+    def _init_rnd(self, cfg: dict, symmetry_cfg, fused_adam: bool):
+        from . import rnd as R
+
+        R.check_rnd_cfg(cfg)
+        for what, on in (("a recurrent policy", self.recurrent),
+                         ("symmetry_cfg data augmentation", self.symmetry is not None
+                          and self.symmetry["use_data_augmentation"]),
+                         ("more than one rank", self.shard.world > 1), ("precision='bf16'", self.precision == "bf16")):
+            if on:
+                raise ValueError(f"rnd_cfg with {what} is not supported")
+        if "num_states" not in cfg:
+            raise ValueError("rnd_cfg: num_states is missing (the runner sets it from the rnd_state observation group)")
+        lr = float(cfg.pop("learning_rate", 1e-3))
+        fused_rnd = cfg.pop("fused", None)
+        if fused_rnd is None:
+            fused_rnd = R.rnd_fused_enabled()
+        cfg.setdefault("activation", "elu")
+        self.rnd = R.RandomNetworkDistillation(device=self.device, **cfg)
+        self.rnd_optimizer = torch.optim.Adam(self.rnd.predictor.parameters(), lr=lr, fused=fused_adam,
+                                              capturable=fused_adam)
+        # opt-in: the intrinsic-reward step of process_env_step on the h12learn_rnd_* kernels (rnd.FusedRND)
+        self.rnd_fused = R.FusedRND(self.rnd) if fused_rnd else None
+        self._n_stats += 1  # the rnd loss: the last column
 
     def init_storage(self, num_envs, num_steps, obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_steps, obs_shape[0],
                                       None if critic_obs_shape is None else critic_obs_shape[0], action_shape[0],
-                                      self.device)
+                                      self.device, None if self.rnd is None else self.rnd.num_states)
 
     # ---- collection
     def act(self, obs, critic_obs):
@@ -707,10 +740,22 @@ class PPO:
 
     def process_env_step(self, rewards, dones, infos):
         r = rewards.clone().float()
+        rnd_state = None
+        if self.rnd is not None:  # r += intrinsic, before the bootstrap (rsl_rl ppo.py)
+            state = infos.get("observations", {}).get("rnd_state")
+            if state is None:
+                raise ValueError("rnd_cfg: the env step returned no 'rnd_state' observation group")
+            state = state.to(self.device)
+            if self.rnd_fused is not None:
+                self.intrinsic_rewards, r, rnd_state = self.rnd_fused(state, r)
+            else:
+                self.intrinsic_rewards, rnd_state = self.rnd.get_intrinsic_reward(state)
+                r += self.intrinsic_rewards
         if "time_outs" in infos:  # bootstrap on time-outs (rsl_rl ppo.py)
             r += self.gamma * (self._values.squeeze(1) * infos["time_outs"].to(self.device).float())
         self.storage.add(self._obs, self._critic_obs if self.storage.t.get("privileged_observations") is not None else None,
-                         self._actions, r, dones.float(), self._values, self._log_prob, self._mu, self._sigma)
+                         self._actions, r, dones.float(), self._values, self._log_prob, self._mu, self._sigma,
+                         rnd_state)
         self.policy.reset(dones)
 
     def compute_returns(self, last_critic_obs):
@@ -842,7 +887,8 @@ class PPO:
                               value_loss_coef=self.value_loss_coef, entropy_coef=self.entropy_coef,
                               use_clipped_value_loss=self.use_clipped_value_loss,
                               lr=self._lr_t if mean.is_cuda and adaptive and self.shard.world == 1 else None,
-                              desired_kl=self.desired_kl, stats_accum=stats if mean.is_cuda and sym is None else None)
+                              desired_kl=self.desired_kl,
+                              stats_accum=stats[:3] if mean.is_cuda and sym is None else None)
             loss, out = PPOHead.apply(mean, value, self.policy.std if kind == "scalar" else self.policy.log_std, head)
             if adaptive and head.lr is None:  # CPU, or several ranks: the KL from the head
                 self._adapt_lr(out[3].clone())
@@ -877,12 +923,22 @@ class PPO:
         self._allreduce_grads()
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         self.optimizer.step()
+        if self.rnd is not None:  # the predictor's own loss, backward and Adam, after the policy's
+            s_b = b["rnd_state"][idx]
+            with torch.no_grad():
+                embedding = self.rnd.target(s_b)
+            rnd_loss = nn.functional.mse_loss(self.rnd.predictor(s_b), embedding)
+            self.rnd_optimizer.zero_grad(set_to_none=True)
+            rnd_loss.backward()
+            self.rnd_optimizer.step()
+            stats[-1:] += rnd_loss.detach()
         if fused:  # value loss, surrogate, entropy: from the head, unless it has added them to stats itself
             parts = [out[1], out[0], out[2]] if head.stats_accum is None else None
         else:
             parts = [value_loss.detach(), surrogate_loss.detach(), entropy.mean().detach()]
         if parts is not None:
-            stats += torch.stack(parts + ([symmetry_loss.detach()] if sym is not None else []))
+            parts = torch.stack(parts + ([symmetry_loss.detach()] if sym is not None else []))
+            stats[:parts.shape[0]] += parts
 
     def _augment(self, obs, actions, idx, obs_type):
         """data_augmentation_func on the rows ``idx``.  h12env.symmetry.augment takes the index itself: gather, mirror
@@ -925,9 +981,13 @@ class PPO:
         def drop_graphs_and_grads():
             self.policy.distribution = None
             self.optimizer.zero_grad(set_to_none=True)
+            if self.rnd is not None:
+                self.rnd_optimizer.zero_grad(set_to_none=True)
 
-        state = TrainingState(self.policy.parameters(), self.optimizer, [self._lr_t, self._g_stats])
-        self._graph, _ = capture(lambda: self._minibatch(b, self._g_idx, self._g_stats), self.device, undo=[state],
+        undo = [TrainingState(self.policy.parameters(), self.optimizer, [self._lr_t, self._g_stats])]
+        if self.rnd is not None:
+            undo.append(TrainingState(self.rnd.predictor.parameters(), self.rnd_optimizer))
+        self._graph, _ = capture(lambda: self._minibatch(b, self._g_idx, self._g_stats), self.device, undo=undo,
                                  before_capture=drop_graphs_and_grads)
         self._graph_key = (mb, tuple((k, v.data_ptr(), tuple(v.shape)) for k, v in sorted(b.items())))
 
@@ -986,10 +1046,14 @@ class PPO:
         self.storage.clear()
         if self._lr_t is not None:
             self.learning_rate = float(self._lr_t)
-        v, sl, en, *sy = (stats / n_updates).tolist()
+        v, sl, en, *rest = (stats / n_updates).tolist()
         out = {"value_function": v, "surrogate": sl, "entropy": en}
-        if sy:
-            out["symmetry"] = sy[0]
+        if self.symmetry is not None:
+            out["symmetry"] = rest[0]
+        if self.rnd is not None:
+            out["rnd"] = rest[-1]
+            if self.rnd_fused is not None:
+                self.rnd_fused.dirty = True  # the predictor moved: re-pack before the next collection step
         return out
 
     def optimizer_state_dict(self) -> dict:
@@ -1076,7 +1140,12 @@ class OnPolicyRunner:
             raise ValueError(f"policy.class_name = {class_name!r}; this runner builds {sorted(classes)}")
         policy = classes[class_name](num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         self.alg_cfg.pop("class_name", None)
-        self.alg_cfg.pop("rnd_cfg", None)
+        if self.alg_cfg.get("rnd_cfg") is not None:  # rsl_rl's runner: num_states and the step_dt factor
+            from .rnd import resolve_rnd_cfg
+
+            self.alg_cfg["rnd_cfg"] = resolve_rnd_cfg(self.alg_cfg["rnd_cfg"], env, extras["observations"])
+        else:
+            self.alg_cfg.pop("rnd_cfg", None)
         if self.alg_cfg.get("symmetry_cfg") is not None:  # rsl_rl hands the env to the augmentation function
             self.alg_cfg["symmetry_cfg"] = {**self.alg_cfg["symmetry_cfg"], "_env": env}
         self.alg = PPO(policy, device=device, shard=self.shard, **self.alg_cfg)
@@ -1118,6 +1187,13 @@ class OnPolicyRunner:
         done_mask: list = []
         done_rew: list = []
         done_len: list = []
+        rnd = getattr(self.alg, "rnd", None) is not None  # extrinsic / intrinsic episode sums, collected as rewbuffer is
+        if rnd:
+            erewbuffer, irewbuffer = deque(maxlen=100), deque(maxlen=100)
+            cur_ereward_sum = torch.zeros(self.env.num_envs, device=self.device)
+            cur_ireward_sum = torch.zeros(self.env.num_envs, device=self.device)
+            done_erew: list = []
+            done_irew: list = []
         start_iter = self.current_learning_iteration
         self._start_iter = start_iter
         tot_iter = start_iter + num_learning_iterations
@@ -1140,7 +1216,13 @@ class OnPolicyRunner:
                         # rsl_rl extends the reward / length deques at every step (a host sync per step);
                         # the finished episodes are recorded on the device and moved once per iteration,
                         # in the same order (step-major, env index within a step)
-                        cur_reward_sum += rewards
+                        if rnd:  # rsl_rl: the logged reward is extrinsic + intrinsic
+                            intrinsic = self.alg.intrinsic_rewards
+                            cur_ereward_sum += rewards
+                            cur_ireward_sum += intrinsic
+                            cur_reward_sum += rewards + intrinsic
+                        else:
+                            cur_reward_sum += rewards
                         cur_episode_length += 1
                         done = dones > 0
                         done_mask.append(done)
@@ -1148,10 +1230,20 @@ class OnPolicyRunner:
                         done_len.append(torch.where(done, cur_episode_length, 0.0))
                         cur_reward_sum.masked_fill_(done, 0.0)
                         cur_episode_length.masked_fill_(done, 0.0)
+                        if rnd:
+                            done_erew.append(torch.where(done, cur_ereward_sum, 0.0))
+                            done_irew.append(torch.where(done, cur_ireward_sum, 0.0))
+                            cur_ereward_sum.masked_fill_(done, 0.0)
+                            cur_ireward_sum.masked_fill_(done, 0.0)
                 if self.log_dir is not None and done_mask:
                     m = torch.stack(done_mask)
                     rewbuffer.extend(torch.stack(done_rew)[m].cpu().tolist())
                     lenbuffer.extend(torch.stack(done_len)[m].cpu().tolist())
+                    if rnd:
+                        erewbuffer.extend(torch.stack(done_erew)[m].cpu().tolist())
+                        irewbuffer.extend(torch.stack(done_irew)[m].cpu().tolist())
+                        done_erew.clear()
+                        done_irew.clear()
                     done_mask.clear()
                     done_rew.clear()
                     done_len.clear()
@@ -1163,6 +1255,7 @@ class OnPolicyRunner:
             stop = time.time()
             learn_time = stop - start
             self.current_learning_iteration = it
+            self._rnd_buffers = (erewbuffer, irewbuffer) if rnd else None
             self._log(it, tot_iter, collection_time, learn_time, loss, ep_infos, rewbuffer, lenbuffer)
             if self.log_dir is not None and it % self.save_interval == 0:
                 self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
@@ -1191,6 +1284,12 @@ class OnPolicyRunner:
         if rewbuffer:
             scalars["Train/mean_reward"] = statistics.mean(rewbuffer)
             scalars["Train/mean_episode_length"] = statistics.mean(lenbuffer)
+        if getattr(self.alg, "rnd", None) is not None:
+            scalars["Rnd/weight"] = self.alg.rnd.weight
+            ebuf, ibuf = getattr(self, "_rnd_buffers", None) or ((), ())
+            if ebuf:
+                scalars["Rnd/mean_extrinsic_reward"] = statistics.mean(ebuf)
+                scalars["Rnd/mean_intrinsic_reward"] = statistics.mean(ibuf)
         self.last_iteration_stats = scalars
         if self.shard.rank != 0:
             return
@@ -1209,7 +1308,8 @@ class OnPolicyRunner:
 
     def _loss_scalars(self, loss: dict) -> dict:
         return {"Loss/value_function": loss["value_function"], "Loss/surrogate": loss["surrogate"],
-                "Loss/entropy": loss["entropy"], **({"Loss/symmetry": loss["symmetry"]} if "symmetry" in loss else {})}
+                "Loss/entropy": loss["entropy"], **({"Loss/symmetry": loss["symmetry"]} if "symmetry" in loss else {}),
+                **({"Loss/rnd": loss["rnd"]} if "rnd" in loss else {})}
 
     def save(self, path: str, infos=None):
         if self.shard.rank != 0:
@@ -1220,6 +1320,9 @@ class OnPolicyRunner:
         if self.empirical_normalization:
             d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
             d["critic_obs_norm_state_dict"] = self.critic_obs_normalizer.state_dict()
+        if getattr(self.alg, "rnd", None) is not None:
+            d["rnd_state_dict"] = self.alg.rnd.rnd_state_dict()
+            d["rnd_optimizer_state_dict"] = self.alg.rnd_optimizer.state_dict()
         torch.save(d, path)
 
     def load(self, path: str, load_optimizer: bool = True):
@@ -1234,7 +1337,17 @@ class OnPolicyRunner:
             raise ValueError(f"{path}: the checkpoint's critic reads {w.shape[1]}-wide observations, this env's "
                              f"critic observation is {mine} wide -- the two were built with different "
                              "--privileged_critic settings (env.observations.critic)")
+        if getattr(self.alg, "rnd", None) is not None and "rnd_state_dict" not in d:
+            raise ValueError(f"{path}: the checkpoint holds no rnd_state_dict, this run trains with rnd_cfg -- resume it "
+                             "without rnd_cfg, or start the RND run afresh")
         self.alg.policy.load_state_dict(d["model_state_dict"])
+        if getattr(self.alg, "rnd", None) is not None:
+            self.alg.rnd.load_rnd_state_dict(d["rnd_state_dict"])
+            if load_optimizer and "rnd_optimizer_state_dict" in d:
+                self.alg.rnd_optimizer.load_state_dict(d["rnd_optimizer_state_dict"])
+            self.alg._graph = None  # the captured graph holds the old optimizer state tensors
+            if self.alg.rnd_fused is not None:
+                self.alg.rnd_fused.dirty = True
         if self.empirical_normalization and "obs_norm_state_dict" in d:
             self.obs_normalizer.load_state_dict(d["obs_norm_state_dict"])
             self.critic_obs_normalizer.load_state_dict(d["critic_obs_norm_state_dict"])
@@ -1283,12 +1396,16 @@ class OnPolicyRunner:
 
     def train_mode(self):
         self.alg.policy.train()
+        if getattr(self.alg, "rnd", None) is not None:
+            self.alg.rnd.train()
         if self.empirical_normalization:
             self.obs_normalizer.train()
             self.critic_obs_normalizer.train()
 
     def eval_mode(self):
         self.alg.policy.eval()
+        if getattr(self.alg, "rnd", None) is not None:
+            self.alg.rnd.eval()
         if self.empirical_normalization:
             self.obs_normalizer.eval()
             self.critic_obs_normalizer.eval()

@@ -18,6 +18,8 @@ OWN_TERMS = TERMS[TERMS.index("base_height"):]
 W_PLANE, W_TERRAIN = 65, 252
 
 PRIV_SYMBOLS = ["h12priv_layout", "h12priv_observe", "h12priv_last_error"]
+# a subset of the row's terms, compacted: the rnd_state group (h12env.rnd)
+PRIV_TERMS_SYMBOLS = ["h12priv_layout_terms", "h12priv_observe_terms"]
 
 
 class PrivConfig(C.Structure):
@@ -39,7 +41,7 @@ def priv_library():
     from ._abi import H12EnvError, load_library
 
     lib = load_library()
-    for s in PRIV_SYMBOLS:
+    for s in PRIV_SYMBOLS + PRIV_TERMS_SYMBOLS:
         if not hasattr(lib, s):
             raise H12EnvError(f"libh12env.so lacks {s}; rebuild it (csrc/h12_priv.hip)")
     i32p = C.POINTER(C.c_int32)
@@ -47,6 +49,11 @@ def priv_library():
     lib.h12priv_layout.restype = C.c_int
     lib.h12priv_observe.argtypes = [C.c_void_p, C.c_int, C.POINTER(PrivConfig), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.h12priv_observe.restype = C.c_int
+    lib.h12priv_layout_terms.argtypes = [C.c_int, C.c_uint32, i32p, C.c_void_p, i32p]
+    lib.h12priv_layout_terms.restype = C.c_int
+    lib.h12priv_observe_terms.argtypes = [C.c_void_p, C.c_int, C.POINTER(PrivConfig), C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p]
+    lib.h12priv_observe_terms.restype = C.c_int
     lib.h12priv_last_error.argtypes = []
     lib.h12priv_last_error.restype = C.c_char_p
     _bound = lib
@@ -75,6 +82,31 @@ def layout(terrain: bool):
     return w.value, [(TERMS[table[3 * i]], table[3 * i + 1], table[3 * i + 2]) for i in range(k.value)]
 
 
+def term_mask(terms) -> int:
+    """The h12priv_observe_terms mask of a collection of term names (bit i: TERMS[i]); ValueError for a name that is
+    not a term or for none at all."""
+    terms = list(terms)
+    unknown = [t for t in terms if t not in TERMS]
+    if unknown:
+        raise ValueError(f"unknown observation terms {unknown} (terms: {TERMS})")
+    if not terms:
+        raise ValueError("no observation terms")
+    mask = 0
+    for t in terms:
+        mask |= 1 << TERMS.index(t)
+    return mask
+
+
+def layout_terms(terrain: bool, mask: int):
+    """(W, [(term name, offset, width)]) of the compacted row of ``mask`` (h12priv_layout_terms: host only)."""
+    lib = priv_library()
+    w, k = C.c_int32(), C.c_int32()
+    table = (C.c_int32 * (3 * len(TERMS)))()
+    check(lib, lib.h12priv_layout_terms(int(bool(terrain)), mask, C.byref(w), table, C.byref(k)),
+          "h12priv_layout_terms")
+    return w.value, [(TERMS[table[3 * i]], table[3 * i + 1], table[3 * i + 2]) for i in range(k.value)]
+
+
 def default_force_scale() -> float:
     """1 / (total model mass x g): a foot force in body weights (the raw ~700 N would swamp a critic that runs
     without empirical normalisation)."""
@@ -89,6 +121,10 @@ def term_scales(cfg) -> dict:
     """term -> scale of the critic row of an env cfg: the policy group's scales for the terms they share, the critic
     group's for its own (feet_force defaults to default_force_scale(), every other term to 1)."""
     crit = cfg.observations.critic
+    if crit is None:  # the rnd_state group without a critic group: the critic row's default scales
+        from .cfg import CriticObsCfg
+
+        crit = CriticObsCfg()
     unknown = set(crit.scales) - set(OWN_TERMS)
     if unknown:
         raise ValueError(f"critic observation scales for unsupported terms: {sorted(unknown)} (own terms: {OWN_TERMS})")
@@ -102,17 +138,17 @@ def term_scales(cfg) -> dict:
 
 
 def priv_config(env) -> PrivConfig:
-    """h12priv_config of an H12VelocityEnv whose cfg has a critic group."""
+    """h12priv_config of an H12VelocityEnv whose cfg has a critic group or an rnd_state group."""
     cfg, cc = env.cfg, env._ccfg
     crit = cfg.observations.critic
-    if crit.history_length not in (0, 1, None):
+    if crit is not None and crit.history_length not in (0, 1, None):
         raise ValueError("the critic observation has no history (history_length 0)")
-    if not crit.concatenate_terms:
+    if crit is not None and not crit.concatenate_terms:
         raise ValueError("the critic observation is one concatenated row (concatenate_terms=True)")
     t = env.terrain
     if (t is None) != (cfg.scene.height_scanner is None):
-        raise ValueError("the critic group needs the heightfield and the height scanner together (a terrain task) or "
-                         "neither (a plane task)")
+        raise ValueError("the critic / rnd_state group needs the heightfield and the height scanner together (a "
+                         "terrain task) or neither (a plane task)")
     c = PrivConfig()
     if t is not None:
         c.terrain = 1

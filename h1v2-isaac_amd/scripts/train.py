@@ -69,6 +69,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_loss", action="store_true", default=False,
                     help="the PPO update's loss head (gathers, losses, gradients, KL schedule) as one fused HIP call "
                          "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
+    rnd = ap.add_argument_group("rnd", "rsl_rl's rnd_cfg: Random Network Distillation, an exploration bonus (h12env.rnd)")
+    rnd.add_argument("--rnd", action="store_true", default=False,
+                     help="add RND's intrinsic reward: sets env.observations.rnd_state (the defaults of RndStateObsCfg) and "
+                          "agent.algorithm.rnd_cfg (RslRlRndCfg defaults; agent.algorithm.rnd_cfg.* can be overridden)")
+    rnd.add_argument("--rnd_weight", type=float, default=None,
+                     help="rnd_cfg.weight before the runner's step_dt factor (default 1.0 with --rnd)")
+    rnd.add_argument("--rnd_fused", action="store_true", default=False,
+                     help="with --rnd: the per-env-step reward work on the h12learn_rnd_* kernels (h12env.rnd.FusedRND; "
+                          "agent.algorithm.rnd_cfg.fused=true works too)")
     ds = ap.add_argument_group("distillation", "rsl_rl's Distillation: a student on the deployable observation group "
                                "(h12env.student) copies a PPO-trained teacher (h12env.distill)")
     ds.add_argument("--distill", action="store_true", default=False,
@@ -97,7 +106,7 @@ def make_distillation(agent_cfg, env_cfg, args):
     from isaaclab_rl.rsl_rl import (RslRlDistillationAlgorithmCfg, RslRlDistillationStudentTeacherCfg,
                                     RslRlDistillationStudentTeacherRecurrentCfg)
 
-    for flag in ("symmetry", "fused_learner", "fused_loss", "recurrent"):
+    for flag in ("symmetry", "fused_learner", "fused_loss", "recurrent", "rnd", "rnd_fused"):
         if getattr(args, flag, None):
             raise SystemExit(f"--distill does not take --{flag} (a PPO option; the student's memory is --student_recurrent)")
     if not args.teacher_checkpoint and not args.resume:
@@ -155,6 +164,20 @@ def make_recurrent(agent_cfg):
         agent_cfg.policy = RslRlPpoActorCriticRecurrentCfg(**kept)
 
 
+def make_rnd(agent_cfg, args):
+    """--rnd: agent.algorithm.rnd_cfg as an RslRlRndCfg with --rnd_weight, unless the task's cfg already has one."""
+    from isaaclab_rl.rsl_rl import RslRlRndCfg
+
+    if agent_cfg.algorithm.rnd_cfg is None:
+        agent_cfg.algorithm.rnd_cfg = RslRlRndCfg(weight=1.0 if args.rnd_weight is None else args.rnd_weight)
+    elif args.rnd_weight is not None:
+        r = agent_cfg.algorithm.rnd_cfg
+        if isinstance(r, dict):
+            r["weight"] = args.rnd_weight
+        else:
+            r.weight = args.rnd_weight
+
+
 def apply_cli(agent_cfg, env_cfg, args):
     """cli_args.update_rsl_rl_cfg + the num_envs / seed / device / max_iterations overrides."""
     for flag, attr in (("seed", "seed"), ("resume", "resume"), ("load_run", "load_run"),
@@ -187,6 +210,20 @@ def apply_cli(agent_cfg, env_cfg, args):
         agent_cfg.algorithm.fused_loss = True
     if getattr(args, "fused_rnn_update", False):
         agent_cfg.algorithm.fused_rnn_update = True
+    r = getattr(agent_cfg.algorithm, "rnd_cfg", None)
+    if getattr(args, "rnd_fused", False):
+        if r is None:
+            raise SystemExit("--rnd_fused needs --rnd (or an agent.algorithm.rnd_cfg override)")
+        if isinstance(r, dict):
+            r["fused"] = True
+        else:
+            r.fused = True
+    elif getattr(args, "rnd_weight", None) is not None and r is None:
+        raise SystemExit("--rnd_weight needs --rnd (or an agent.algorithm.rnd_cfg override)")
+    if r is not None:  # the group RND reads; an env cfg that has set it keeps its terms
+        from h12env.cfg import enable_rnd_state
+
+        enable_rnd_state(env_cfg)
     if getattr(args, "privileged_critic", False):
         from h12env.cfg import enable_privileged_critic
 
@@ -230,6 +267,8 @@ def main(argv=None) -> int:
         make_distillation(agent_cfg, env_cfg, args)
     elif args.recurrent:  # before the overrides, so that agent.policy.rnn_* exist for them
         make_recurrent(agent_cfg)
+    if args.rnd and not args.distill:  # before the overrides, so that agent.algorithm.rnd_cfg.* exist for them
+        make_rnd(agent_cfg, args)
     apply_overrides(env_cfg, agent_cfg, hydra_args)
     apply_cli(agent_cfg, env_cfg, args)
     rank = dist.get_rank() if dist.is_initialized() else 0

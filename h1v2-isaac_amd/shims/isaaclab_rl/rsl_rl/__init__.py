@@ -40,6 +40,23 @@ class RslRlSymmetryCfg:
 
 
 @dataclass
+class RslRlRndCfg:
+    """rsl_rl 2.3 Random Network Distillation options (isaaclab_rl.rsl_rl.rnd_cfg.RslRlRndCfg; h12env.rnd).  The env
+    must serve the observation group "rnd_state" (env_cfg.observations.rnd_state).  weight_schedule is None or a dict
+    {"mode": "constant" | "step" | "linear", ...}; -1 in the hidden dims means the width of rnd_state."""
+    weight: float = 0.0
+    weight_schedule: dict | None = None
+    reward_normalization: bool = False
+    state_normalization: bool = False
+    learning_rate: float = 1.0e-3
+    num_outputs: int = 1
+    predictor_hidden_dims: list = field(default_factory=lambda: [-1])
+    target_hidden_dims: list = field(default_factory=lambda: [-1])
+    # h12env.rnd extension: the per-env-step reward work on the h12learn_rnd_* kernels (None: H12_RND_FUSED)
+    fused: bool | None = None
+
+
+@dataclass
 class RslRlPpoAlgorithmCfg:
     class_name: str = "PPO"
     num_learning_epochs: int = 5
@@ -56,7 +73,7 @@ class RslRlPpoAlgorithmCfg:
     clip_param: float = 0.2
     normalize_advantage_per_mini_batch: bool = False
     symmetry_cfg: RslRlSymmetryCfg | dict | None = None
-    rnd_cfg: dict | None = None
+    rnd_cfg: RslRlRndCfg | dict | None = None
     # h12env.ppo extension: actor and critic of the update on the fused HIP forward / backward (None: H12_LEARNER_FUSED)
     fused_learner: bool | None = None
     # h12env.ppo extension: the update's loss head as one HIP call, h12env.ppo_head.PPOHead (None: H12_PPO_HEAD_FUSED)
@@ -220,5 +237,5 @@ def export_policy_as_onnx(policy, normalizer, path: str, filename="policy.onnx",
 
 __all__ = ["RslRlDistillationAlgorithmCfg", "RslRlDistillationStudentTeacherCfg",
            "RslRlDistillationStudentTeacherRecurrentCfg", "RslRlOnPolicyRunnerCfg", "RslRlPpoActorCriticCfg",
-           "RslRlPpoAlgorithmCfg", "RslRlSymmetryCfg", "RslRlVecEnvWrapper", "export_policy_as_jit",
+           "RslRlPpoAlgorithmCfg", "RslRlRndCfg", "RslRlSymmetryCfg", "RslRlVecEnvWrapper", "export_policy_as_jit",
            "export_policy_as_onnx"]

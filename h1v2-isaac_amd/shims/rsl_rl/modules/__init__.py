@@ -1,4 +1,6 @@
 from h12env.distill import StudentTeacher, StudentTeacherRecurrent
 from h12env.ppo import ActorCritic, EmpiricalNormalization
+from h12env.rnd import EmpiricalDiscountedVariationNormalization, RandomNetworkDistillation
 
-__all__ = ["ActorCritic", "EmpiricalNormalization", "StudentTeacher", "StudentTeacherRecurrent"]
+__all__ = ["ActorCritic", "EmpiricalDiscountedVariationNormalization", "EmpiricalNormalization",
+           "RandomNetworkDistillation", "StudentTeacher", "StudentTeacherRecurrent"]

@@ -1,5 +1,6 @@
 /* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
- * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_policy_rnn_train.hip, csrc/h12_ppo_head.hip).
+ * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_policy_rnn_train.hip, csrc/h12_rnd.hip,
+ * csrc/h12_ppo_head.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
@@ -306,6 +307,54 @@ int h12learn_lstm_seq_forward(const h12learn_lstm_seq_desc* desc, const float* p
                               void* stream);
 int h12learn_lstm_seq_backward(const h12learn_lstm_seq_desc* desc, const float* packed,
                                const h12learn_lstm_seq_grad_io* io, void* stream);
+
+/* ---- Random Network Distillation's per-env-step work (csrc/h12_rnd.hip; h12env/rnd.py): the
+ * intrinsic reward of one collection step in two launches.
+ *
+ * h12learn_rnd_reward, one launch.  desc.n_nets == 2: nets[0] is the predictor, nets[1] the target, both over the
+ * normalised x ([n][d_in] contiguous fp32; norm_* as for h12learn_mlp_forward); their depths and hidden widths may
+ * differ, their last widths are equal.  packed is h12learn_mlp_pack of the same desc (the W / b pointers are not read):
+ * repack after every change of the predictor.  Per row r:
+ *     err[r] = sqrtf(sum_j (target(xn_r)[j] - predictor(xn_r)[j])^2)
+ * Both embeddings come from the tile routines of h12learn_mlp_forward and carry its bits; the squares are summed in a
+ * fixed order (the 16 columns of a tile by an xor butterfly, a wave's tiles in order, the four waves in order) that
+ * depends on the output width alone, never on n or the grid.  xn (may be null) receives the normalised rows [n][d_in];
+ * emb (may be null; a test hook) is float*[2] and receives the predictor's and the target's embedding [n][d_out].
+ * Every width up to h12learn_mlp_max_width(); a block holds the input tile, two hidden images and the embedding, 16 rows
+ * each, in LDS, and widths whose images exceed a CU's 160 KiB are H12LEARN_E_ARG.  More than 64 KiB: the first such
+ * call raises the kernel's limit and fails with H12LEARN_E_HIP when its stream is capturing. */
+int h12learn_rnd_reward(const h12learn_mlp_desc* desc, const float* packed, const float* x, long long n, float* err,
+                        float* xn, float* const* emb, void* stream);
+
+/* h12learn_rnd_finish, one launch of one block.  With normalize != 0 (rnd.EmpiricalDiscountedVariationNormalization):
+ *     avg[i]  = *first ? err[i] : avg[i] * gamma + err[i]          separately rounded; *first is then set to 0
+ *     while *count < until: the scalar statistics take the batch mean and population variance of avg by
+ *         ppo.EmpiricalNormalization's rule (count += n; rate = n / count; delta = mean_x - mean; mean += rate delta;
+ *         var += rate (var_x - var + delta (mean_x - mean)); std = sqrt(var))
+ *     v[i]    = *std > 0 ? err[i] / *std : err[i]                  with the statistics just updated
+ * and v = err otherwise (the statistics pointers are then not read).  Then, separately rounded,
+ *     intrinsic[i] = v[i] * *weight;   total[i] = ext_reward[i] + intrinsic[i].
+ * The sums are fp32: a thread folds its elements in index order, a wave its lanes by an xor butterfly, the block its
+ * waves in order.  The same inputs give the same bits; n >= 1.  intrinsic / total may alias nothing else. */
+typedef struct h12learn_rnd_finish_args {
+  long long n;
+  int normalize;
+  float gamma;
+  long long until;
+  const float* err;        /* [n] */
+  const float* ext_reward; /* [n] */
+  const float* weight;     /* device scalar */
+  float* avg;              /* [n] */
+  float* mean;             /* device scalars */
+  float* var;
+  float* std;
+  long long* count;
+  int* first;
+  float* intrinsic;        /* [n] */
+  float* total;            /* [n] */
+} h12learn_rnd_finish_args;
+
+int h12learn_rnd_finish(const h12learn_rnd_finish_args* args, void* stream);
 
 /* ---- fused PPO loss head (csrc/h12_ppo_head.hip): everything PPO._minibatch (h12env/ppo.py) computes between the
  * networks' outputs and loss.backward(), in two launches: the minibatch gathers of the per-sample tensors, the Gaussian

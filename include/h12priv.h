@@ -72,6 +72,15 @@ int h12priv_layout(int terrain, int32_t* width, int32_t table[H12PRIV_NTERMS][3]
  * foot_force: device [n][2] (h12env_step_out.foot_force) or NULL (zeros); out: device [n][W]. */
 int h12priv_observe(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force, float* out,
                     void* stream);
+/* A subset of the row's terms, compacted (the rnd_state group, h12env/rnd.py): term_mask has bit H12PRIV_T_x set for
+ * every term that is written, in row order; out is device [n][W'] with W' the sum of their widths.  The rows are built
+ * by the device code of h12priv_observe, so every column holds the bits of the same column of the full row; ONE launch.
+ * A mask that names no term, a term past the table, or height_scan without cfg.terrain is H12PRIV_E_ARG.
+ * h12priv_layout_terms (host only) gives W' and the (term id, offset, width) rows of the compacted row. */
+int h12priv_layout_terms(int terrain, uint32_t term_mask, int32_t* width, int32_t table[H12PRIV_NTERMS][3],
+                         int32_t* n_terms);
+int h12priv_observe_terms(const void* workspace, int n, const h12priv_config* cfg, const float* foot_force,
+                          uint32_t term_mask, float* out, void* stream);
 const char* h12priv_last_error(void);
 
 #ifdef __cplusplus

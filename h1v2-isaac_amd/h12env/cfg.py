@@ -78,8 +78,48 @@ class SimCfg:
 
 
 @dataclass
+class HfRandomUniformTerrainCfg:
+    """isaaclab.terrains.HfRandomUniformTerrainCfg: per-pixel noise from noise_range in steps of noise_step."""
+    proportion: float = 1.0
+    noise_range: tuple = (0.02, 0.10)
+    noise_step: float = 0.02
+    border_width: float = 0.25
+
+
+@dataclass
+class HfPyramidSlopedTerrainCfg:
+    """isaaclab.terrains.HfPyramidSlopedTerrainCfg: a sloped pyramid cut off at a central platform."""
+    proportion: float = 1.0
+    slope_range: tuple = (0.0, 0.4)
+    platform_width: float = 2.0
+    border_width: float = 0.25
+    inverted: bool = False
+
+
+@dataclass
+class MeshPyramidStairsTerrainCfg:
+    """isaaclab.terrains.MeshPyramidStairsTerrainCfg (inverted: MeshInvertedPyramidStairsTerrainCfg)."""
+    proportion: float = 1.0
+    step_height_range: tuple = (0.05, 0.23)
+    step_width: float = 0.3
+    platform_width: float = 3.0
+    border_width: float = 1.0
+    inverted: bool = False
+
+
+@dataclass
+class MeshRandomGridTerrainCfg:
+    """isaaclab.terrains.MeshRandomGridTerrainCfg: a grid of boxes at random heights around a platform."""
+    proportion: float = 1.0
+    grid_width: float = 0.45
+    grid_height_range: tuple = (0.05, 0.2)
+    platform_width: float = 2.0
+
+
+@dataclass
 class TerrainGeneratorCfg:
-    """ROUGH_TERRAINS_CFG (biped_tasks/utils/mdp/terrains.py:11-28): one HfRandomUniform sub-terrain type."""
+    """ROUGH_TERRAINS_CFG (biped_tasks/utils/mdp/terrains.py:11-28): one HfRandomUniform sub-terrain type, or with
+    sub_terrains a mix of types as isaaclab.terrains.TerrainGeneratorCfg holds it (isaaclab_rough_terrains_cfg)."""
     size: tuple = (8.0, 8.0)
     border_width: float = 20.0
     num_rows: int = 10
@@ -92,6 +132,117 @@ class TerrainGeneratorCfg:
     noise_range: tuple = (0.0, 0.02)
     noise_step: float = 0.005
     sub_border_width: float = 0.25
+    # name -> sub-terrain cfg (the classes above); None: the single type of the fields above
+    sub_terrains: dict | None = field(default=None, metadata={"omit_if_none": True})
+    # (dumped only when it differs from its default, so that the single-type dumps stay what they were)
+    difficulty_range: tuple = field(default=(0.0, 1.0), metadata={"omit_if_default": True})
+    # cell size of the stitched field the kernels sample; None: horizontal_scale
+    raster_scale: float | None = field(default=None, metadata={"omit_if_none": True})
+
+
+def isaaclab_rough_terrains_cfg() -> TerrainGeneratorCfg:
+    """isaaclab.terrains.config.rough.ROUGH_TERRAINS_CFG (IsaacLab 2.1.0), the terrain of upstream's
+    LocomotionVelocityRoughEnvCfg and so of the reference's H12_12dof_RoughEnvCfg.  The values are restated from the
+    published configuration and are not pinned against the package: a correction is one line here."""
+    stairs = dict(step_height_range=(0.05, 0.23), step_width=0.3, platform_width=3.0, border_width=1.0)
+    slope = dict(slope_range=(0.0, 0.4), platform_width=2.0, border_width=0.25)
+    return TerrainGeneratorCfg(
+        size=(8.0, 8.0), border_width=20.0, num_rows=10, num_cols=20, horizontal_scale=0.1, vertical_scale=0.005,
+        slope_threshold=0.75, curriculum=True, difficulty_range=(0.0, 1.0), raster_scale=0.05,
+        sub_terrains={
+            "pyramid_stairs": MeshPyramidStairsTerrainCfg(proportion=0.2, **stairs),
+            "pyramid_stairs_inv": MeshPyramidStairsTerrainCfg(proportion=0.2, inverted=True, **stairs),
+            "boxes": MeshRandomGridTerrainCfg(proportion=0.2, grid_width=0.45, grid_height_range=(0.05, 0.2),
+                                              platform_width=2.0),
+            "random_rough": HfRandomUniformTerrainCfg(proportion=0.2, noise_range=(0.02, 0.10), noise_step=0.02,
+                                                      border_width=0.25),
+            "hf_pyramid_slope": HfPyramidSlopedTerrainCfg(proportion=0.1, **slope),
+            "hf_pyramid_slope_inv": HfPyramidSlopedTerrainCfg(proportion=0.1, inverted=True, **slope),
+        })
+
+
+SUB_TERRAIN_CLASSES = (HfRandomUniformTerrainCfg, HfPyramidSlopedTerrainCfg, MeshPyramidStairsTerrainCfg,
+                       MeshRandomGridTerrainCfg)
+
+
+def sub_terrain_class(d: dict):
+    """The sub-terrain cfg class a dumped table entry (class_to_dict, params/env.yaml) belongs to: the one whose
+    field names are the entry's keys."""
+    import dataclasses
+
+    for c in SUB_TERRAIN_CLASSES:
+        if {f.name for f in dataclasses.fields(c)} == set(d):
+            return c
+    raise ValueError(f"no sub-terrain cfg has the fields {sorted(d)}")
+
+
+def terrain_generator_from_dict(d: dict) -> TerrainGeneratorCfg:
+    """TerrainGeneratorCfg from its dump (class_to_dict / params/env.yaml), the sub-terrain table included."""
+    import dataclasses
+
+    tup = {f.name for f in dataclasses.fields(TerrainGeneratorCfg) if f.type.startswith("tuple")}
+    kw = {k: (tuple(v) if k in tup and v is not None else v) for k, v in d.items() if k != "sub_terrains"}
+    g = TerrainGeneratorCfg(**kw)
+    subs = d.get("sub_terrains")
+    if subs is not None:
+        g.sub_terrains = {name: sub_terrain_class(s)(**{k: (tuple(v) if isinstance(v, list) else v)
+                                                        for k, v in s.items()}) for name, s in subs.items()}
+    return g
+
+
+def enable_reference_rough_terrain(env_cfg):
+    """Put upstream's ROUGH_TERRAINS_CFG (isaaclab_rough_terrains_cfg) on a terrain task's cfg (Rough, C5), keeping
+    max_init_terrain_level and the curriculum term as the cfg has them; a PLAY cfg (curriculum off on its generator)
+    keeps its 5 x 5 grid without curriculum, as rough_env_cfg.py:138-144 shrinks it."""
+    t = env_cfg.scene.terrain
+    if t.terrain_type != "generator" or t.terrain_generator is None:
+        raise ValueError("the reference's rough terrain needs a terrain task (scene.terrain.terrain_type = "
+                         "'generator'); this cfg runs on the plane")
+    old = t.terrain_generator
+    g = isaaclab_rough_terrains_cfg()
+    if not old.curriculum:
+        g.num_rows, g.num_cols, g.curriculum = old.num_rows, old.num_cols, False
+    t.terrain_generator = g
+    return env_cfg
+
+
+TERRAIN_CHOICES = ("project", "isaaclab_rough")
+
+
+def apply_terrain_choice(env_cfg, choice: str | None):
+    """The scripts' --terrain flag: "project" (default) leaves the task's terrain, "isaaclab_rough" puts the
+    reference's on a terrain task and is refused, with a message, on a task that runs on the plane."""
+    if choice in (None, "project"):
+        return env_cfg
+    if choice != "isaaclab_rough":
+        raise SystemExit(f"--terrain {choice}: choose from {', '.join(TERRAIN_CHOICES)}")
+    try:
+        return enable_reference_rough_terrain(env_cfg)
+    except ValueError as e:
+        raise SystemExit(f"--terrain isaaclab_rough: {e}") from None
+
+
+def terrain_from_run(env_cfg, run_dir):
+    """play.py: a run trained on a sub-terrain mix plays on it -- the table is read from the run's params/env.yaml
+    (what train.py dumps), not from a flag.  The playing cfg keeps its own grid size and curriculum switch (the PLAY
+    tasks' 5 x 5 without curriculum).  Returns whether the run had a mix."""
+    import os
+
+    import yaml
+
+    path = os.path.join(str(run_dir), "params", "env.yaml")
+    t = env_cfg.scene.terrain
+    if t.terrain_generator is None or not os.path.exists(path):
+        return False
+    with open(path) as f:
+        d = ((((yaml.safe_load(f) or {}).get("scene") or {}).get("terrain") or {}).get("terrain_generator")) or {}
+    if not d.get("sub_terrains"):
+        return False
+    old = t.terrain_generator
+    g = terrain_generator_from_dict(d)
+    g.num_rows, g.num_cols, g.curriculum = old.num_rows, old.num_cols, old.curriculum
+    t.terrain_generator = g
+    return True
 
 
 @dataclass

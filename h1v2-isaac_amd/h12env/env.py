@@ -488,6 +488,15 @@ class H12VelocityEnv:
         self._log_ptr = self._log_ring.data_ptr()
         self._log_extra = ({"Curriculum/terrain_levels": lambda: self.terrain_levels().mean()}
                            if self.terrain is not None else None)
+        if self.terrain is not None:
+            # a mix of sub-terrain types: also the mean level of the envs in each type's columns (an env keeps its
+            # column; the weights are built once, the mean is one device dot product when the log is read)
+            from .terrain import level_log_weights
+
+            col = (self._istate[_abi.I["TERRAIN"][0]] >> 16).cpu().numpy()
+            for key, w in level_log_weights(self.terrain, col).items():
+                w = torch.from_numpy(w).to(self.device)
+                self._log_extra[key] = lambda w=w: self.terrain_levels() @ w
 
     # ------------------------------------------------------------------ properties (ManagerBasedEnv)
     @property

@@ -85,6 +85,8 @@ def main(argv=None) -> int:
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="build the env with the privileged critic observation group, as train.py / play.py do with "
                          "this flag (the exported policy is the actor alone: the evaluation itself does not change)")
+    ap.add_argument("--terrain", default="project", choices=["project", "isaaclab_rough"],
+                    help="as train.py / play.py; the evaluation runs on the plane, which refuses isaaclab_rough")
     args = ap.parse_args(argv)
     if not 0 <= args.trace_envs <= args.num_envs:
         ap.error("--trace_envs must be in 0..num_envs")
@@ -106,6 +108,9 @@ def main(argv=None) -> int:
     cfg.scene.num_envs = args.num_envs
     cfg.sim.device = args.device
     cfg.decimation = int(round(pcfg["control_dt"] / cfg.sim.dt))
+    from h12env.cfg import apply_terrain_choice
+
+    apply_terrain_choice(cfg, args.terrain)
     if args.privileged_critic:
         from h12env.cfg import enable_privileged_critic
 

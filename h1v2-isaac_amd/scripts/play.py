@@ -34,6 +34,9 @@ def main(argv=None) -> int:
     ap.add_argument("--privileged_critic", action="store_true", default=False,
                     help="the checkpoint was trained with train.py --privileged_critic (its critic reads the "
                          "privileged observation group)")
+    ap.add_argument("--terrain", default="project", choices=["project", "isaaclab_rough"],
+                    help="terrain of a terrain task for a run whose params/env.yaml does not say: a run trained with "
+                         "train.py --terrain isaaclab_rough plays on that mix without this flag; refused on plane tasks")
     ap.add_argument("--video", action="store_true", default=False, help="Record a video of the rollout.")
     ap.add_argument("--video_length", type=int, default=200, help="Length of the recorded video (in steps).")
     args = ap.parse_args(argv)
@@ -57,9 +60,15 @@ def main(argv=None) -> int:
 
         enable_privileged_critic(env_cfg)
     env_cfg.sim.device = agent_cfg.device = args.device
+    from h12env.cfg import apply_terrain_choice, terrain_from_run
+
+    apply_terrain_choice(env_cfg, args.terrain)
     root = os.path.abspath(os.path.join("logs", "rsl_rl", args.experiment_name or agent_cfg.experiment_name))
     path = get_checkpoint_path(root, args.load_run, args.checkpoint)
     print(f"[INFO]: Loading model checkpoint from: {path}")
+    if terrain_from_run(env_cfg, os.path.dirname(path)):  # the run's own sub-terrain mix, read from its cfg
+        print("[INFO]: playing on the run's sub-terrain mix: "
+              + ", ".join(env_cfg.scene.terrain.terrain_generator.sub_terrains))
     # a recurrent checkpoint (train.py --recurrent) says so itself: the memory's type and size are read from it
     keys = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
     # a distilled student (train.py --distill) says so too: it has student.* parameters.  The env then returns the

@@ -40,6 +40,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--task", type=str, default="Isaac-Velocity-Flat-H12_12dof-v0")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--max_iterations", type=int, default=None)
+    ap.add_argument("--terrain", type=str, default="project", choices=["project", "isaaclab_rough"],
+                    help="terrain of a terrain task: its own (project: one noise type, 0-2 cm) or the reference's Rough mix "
+                         "(isaaclab_rough: upstream ROUGH_TERRAINS_CFG, h12env.cfg.isaaclab_rough_terrains_cfg); "
+                         "env.scene.terrain.terrain_generator.* overrides reach either; refused on plane tasks")
     rl = ap.add_argument_group("rsl_rl")
     rl.add_argument("--experiment_name", type=str, default=None)
     rl.add_argument("--run_name", type=str, default=None)
@@ -263,6 +267,9 @@ def main(argv=None) -> int:
 
     env_cfg = load_cfg_from_registry(args.task, "env_cfg_entry_point")
     agent_cfg = load_cfg_from_registry(args.task, "rsl_rl_cfg_entry_point")
+    from h12env.cfg import apply_terrain_choice
+
+    apply_terrain_choice(env_cfg, args.terrain)  # before the overrides, so that ...terrain_generator.sub_terrains.* exist
     if args.distill:  # before the overrides, so that agent.algorithm.gradient_length etc. exist for them
         make_distillation(agent_cfg, env_cfg, args)
     elif args.recurrent:  # before the overrides, so that agent.policy.rnn_* exist for them

@@ -13,6 +13,8 @@ def class_to_dict(obj):
             v = getattr(obj, f.name)
             if v is None and f.metadata.get("omit_if_none"):
                 continue  # an optional group that is off leaves the dump as it was before the field existed
+            if f.metadata.get("omit_if_default") and v == f.default:
+                continue  # likewise a later field that still has its default
             out[f.name] = class_to_dict(v)
         return out
     if isinstance(obj, dict):

@@ -18,9 +18,7 @@ a chunk that spans an epoch boundary is two such calls, since every epoch restar
 from __future__ import annotations
 
 import os
-import time
 import warnings
-from collections import deque
 
 import torch
 import torch.nn as nn
@@ -28,7 +26,7 @@ from torch.distributions import Normal
 
 from . import distributed as D
 from .policy import fused_collection_on
-from .ppo import EmpiricalNormalization, OnPolicyRunner, _Logger, _shard_from_env, mlp
+from .ppo import OnPolicyRunner, _DeviceLrAdam, mlp
 from .recurrent import Memory, lstm_sequence_state, state_tensors
 
 POLICY_CLASSES = ("StudentTeacher", "StudentTeacherRecurrent")
@@ -329,9 +327,11 @@ def update_segments(num_steps: int, epochs: int, gradient_length: int):
     return chunks
 
 
-class Distillation:
+class Distillation(_DeviceLrAdam):
     """rsl_rl 2.3's Distillation: behaviour cloning of the teacher's action on the student's own rollouts, truncated
     BPTT every ``gradient_length`` steps, Adam over the policy's parameters, no gradient clipping."""
+
+    rnd = None  # no reward to add an exploration bonus to (the runner refuses rnd_cfg)
 
     def __init__(self, policy, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, loss_type="mse",
                  device="cpu", fused_rnn_update: bool | None = None, shard: D.Shard | None = None, **kwargs):
@@ -343,11 +343,7 @@ class Distillation:
             raise ValueError("Distillation runs on one GPU (the update is a sequence over every env of the rollout)")
         self.policy = policy.to(device)
         self.device = device
-        fused = str(device).startswith("cuda")
-        self._lr_t = torch.tensor(float(learning_rate), device=device) if fused else None
-        self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
-                                          fused=fused, capturable=fused)
-        self.learning_rate = learning_rate
+        self._init_optimizer(learning_rate)
         self.num_learning_epochs = int(num_learning_epochs)
         self.gradient_length = int(gradient_length)
         if self.gradient_length < 1 or self.num_learning_epochs < 1:
@@ -500,23 +496,6 @@ class Distillation:
         self._student_stale = True
         return {"behavior": mean_loss / total}
 
-    def optimizer_state_dict(self) -> dict:
-        """The optimizer state with a plain-float learning rate (rsl_rl's checkpoint layout)."""
-        sd = self.optimizer.state_dict()
-        for g in sd["param_groups"]:
-            if torch.is_tensor(g["lr"]):
-                g["lr"] = float(g["lr"])
-        return sd
-
-    def load_optimizer_state_dict(self, sd: dict):
-        self.optimizer.load_state_dict(sd)
-        lr = float(self.optimizer.param_groups[0]["lr"])
-        self.learning_rate = lr
-        if self._lr_t is not None:
-            self._lr_t.fill_(lr)
-            for g in self.optimizer.param_groups:
-                g["lr"] = self._lr_t
-
     def broadcast_parameters(self):
         pass  # one GPU
 
@@ -541,13 +520,10 @@ class DistillationRunner(OnPolicyRunner):
     observation groups the two networks read; the default is {"student": "student", "teacher": "policy"} -- the teacher
     reads the group it was trained on (rsl_rl 2.3 calls that group "teacher")."""
 
-    def __init__(self, env, train_cfg: dict, log_dir: str | None = None, device="cpu"):
-        self.cfg = train_cfg
-        self.alg_cfg = dict(train_cfg["algorithm"])
-        self.policy_cfg = dict(train_cfg["policy"])
-        self.device = device
-        self.env = env
-        self.shard = getattr(env, "shard", None) or _shard_from_env()
+    _inference_modules = ("memory_s", "student")
+
+    def _build_algorithm(self):
+        env, device = self.env, self.device
         if self.shard.world > 1:
             raise ValueError("Distillation runs on one GPU: start it without torchrun (several GPUs are not supported)")
         if self.alg_cfg.get("symmetry_cfg") is not None:
@@ -557,37 +533,21 @@ class DistillationRunner(OnPolicyRunner):
             raise ValueError("rnd_cfg is not supported with Distillation (there is no reward to add an exploration "
                              "bonus to)")
         class_name = self.policy_cfg.pop("class_name")
-        self.empirical_normalization = bool(train_cfg.get("empirical_normalization", False))
         if self.empirical_normalization and class_name == "StudentTeacherRecurrent":
             raise ValueError("empirical_normalization is not supported with a recurrent student: the update's sequence "
                              "form reads the stored observations as they are")
-        torch.manual_seed(int(train_cfg.get("seed", 1)) + self.shard.rank)
-        self.obs_groups = {**DEFAULT_OBS_GROUPS, **(train_cfg.get("obs_groups") or {})}
+        self.obs_groups = {**DEFAULT_OBS_GROUPS, **(self.cfg.get("obs_groups") or {})}
         s_obs, t_obs = self._split(env.get_observations()[1])
         cls = {"StudentTeacher": StudentTeacher, "StudentTeacherRecurrent": StudentTeacherRecurrent}[class_name]
         policy = cls(s_obs.shape[1], t_obs.shape[1], env.num_actions, **self.policy_cfg).to(device)
         for k in ("class_name", "rnd_cfg", "symmetry_cfg"):
             self.alg_cfg.pop(k, None)
         self.alg = Distillation(policy, device=device, shard=self.shard, **self.alg_cfg)
-        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
-        self.save_interval = int(train_cfg.get("save_interval", 50))
-        if self.empirical_normalization:
-            self.obs_normalizer = EmpiricalNormalization([s_obs.shape[1]], until=1.0e8).to(device)
-            self.teacher_obs_normalizer = EmpiricalNormalization([t_obs.shape[1]], until=1.0e8).to(device)
-            self.teacher_obs_normalizer.eval()  # the teacher's statistics come with its checkpoint and stay
-        else:
-            self.obs_normalizer = nn.Identity().to(device)
-            self.teacher_obs_normalizer = nn.Identity().to(device)
+        self.obs_normalizer = self._normalizer(s_obs.shape[1])
+        self.teacher_obs_normalizer = self._normalizer(t_obs.shape[1])
+        self.teacher_obs_normalizer.eval()  # the teacher's statistics come with its checkpoint and stay
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [s_obs.shape[1]], [t_obs.shape[1]],
                               [env.num_actions])
-        self.log_dir = log_dir
-        self.logger = _Logger(log_dir, self.shard.rank)
-        self.tot_timesteps = 0
-        self.tot_time = 0.0
-        self.current_learning_iteration = 0
-        self.git_status_repos: list[str] = []
-        self.last_iteration_stats: dict = {}
-        self.env.reset()
 
     def _split(self, extras):
         """(student observation, teacher observation) of a step's extras["observations"]."""
@@ -602,80 +562,29 @@ class DistillationRunner(OnPolicyRunner):
             out.append(groups[name])
         return out
 
-    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False):
+    def _check_ready(self):
         if not self.alg.policy.loaded_teacher:
             raise ValueError("Distillation needs a trained teacher: load a PPO checkpoint first "
                              "(runner.load(path), train.py --teacher_checkpoint PATH)")
-        if init_at_random_ep_len:
-            self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf,
-                                                             high=int(self.env.max_episode_length))
-        s_obs, t_obs = (x.to(self.device) for x in self._split(self.env.get_observations()[1]))
-        s_obs, t_obs = self.obs_normalizer(s_obs), self.teacher_obs_normalizer(t_obs)
-        self.train_mode()
-        self._store_git_state()
-        ep_infos: list[dict] = []
-        rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
-        cur_reward_sum = torch.zeros(self.env.num_envs, device=self.device)
-        cur_episode_length = torch.zeros(self.env.num_envs, device=self.device)
-        done_mask, done_rew, done_len = [], [], []
-        start_iter = self.current_learning_iteration
-        self._start_iter = start_iter
-        tot_iter = start_iter + num_learning_iterations
-        for it in range(start_iter, tot_iter):
-            start = time.time()
-            with torch.inference_mode():
-                for _ in range(self.num_steps_per_env):
-                    actions = self.alg.act(s_obs, t_obs)
-                    _, rewards, dones, infos = self.env.step(actions.to(self.env.device))
-                    rewards, dones = rewards.to(self.device), dones.to(self.device)
-                    s_obs, t_obs = (x.to(self.device) for x in self._split(infos))
-                    s_obs, t_obs = self.obs_normalizer(s_obs), self.teacher_obs_normalizer(t_obs)
-                    self.alg.process_env_step(rewards, dones, infos)
-                    if self.log_dir is not None:
-                        if "episode" in infos:
-                            ep_infos.append(infos["episode"])
-                        elif "log" in infos:
-                            ep_infos.append(infos["log"])
-                        cur_reward_sum += rewards
-                        cur_episode_length += 1
-                        done = dones > 0
-                        done_mask.append(done)
-                        done_rew.append(torch.where(done, cur_reward_sum, 0.0))
-                        done_len.append(torch.where(done, cur_episode_length, 0.0))
-                        cur_reward_sum.masked_fill_(done, 0.0)
-                        cur_episode_length.masked_fill_(done, 0.0)
-                if self.log_dir is not None and done_mask:
-                    m = torch.stack(done_mask)
-                    rewbuffer.extend(torch.stack(done_rew)[m].cpu().tolist())
-                    lenbuffer.extend(torch.stack(done_len)[m].cpu().tolist())
-                    done_mask.clear()
-                    done_rew.clear()
-                    done_len.clear()
-            stop = time.time()
-            collection_time = stop - start
-            start = stop
-            loss = self.alg.update()
-            stop = time.time()
-            self.current_learning_iteration = it
-            self._log(it, tot_iter, collection_time, stop - start, loss, ep_infos, rewbuffer, lenbuffer)
-            if self.log_dir is not None and it % self.save_interval == 0:
-                self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
-            ep_infos.clear()
-        self.current_learning_iteration = tot_iter
-        if self.log_dir is not None:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+    def _first_inputs(self):
+        """The first (student, teacher) observations go through the normalisers, as every later pair."""
+        return self._step_inputs(*self.env.get_observations())
+
+    def _step_inputs(self, obs, infos):
+        s_obs, t_obs = (x.to(self.device) for x in self._split(infos))
+        return self.obs_normalizer(s_obs), self.teacher_obs_normalizer(t_obs)
+
+    def _end_collection(self, teacher_obs):
+        pass  # no returns to compute: the update reads the stored teacher actions
 
     def _loss_scalars(self, loss: dict) -> dict:
         return {"Loss/behavior": float(loss["behavior"])}  # the device scalar is read here, at the iteration's log line
 
-    def save(self, path: str, infos=None):
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        d = {"model_state_dict": self.alg.policy.state_dict(), "optimizer_state_dict": self.alg.optimizer_state_dict(),
-             "iter": self.current_learning_iteration, "infos": infos}
-        if self.empirical_normalization:
-            d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
-            d["privileged_obs_norm_state_dict"] = self.teacher_obs_normalizer.state_dict()
-        torch.save(d, path)
+    def _checkpoint_extras(self) -> dict:
+        if not self.empirical_normalization:
+            return {}
+        return {"privileged_obs_norm_state_dict": self.teacher_obs_normalizer.state_dict()}
 
     def load(self, path: str, load_optimizer: bool = True):
         """A PPO checkpoint: its actor becomes the teacher (and its observation normaliser the teacher's), the student
@@ -706,40 +615,5 @@ class DistillationRunner(OnPolicyRunner):
         self.alg._fused = None  # the fused wrappers are packed from the parameters: rebuilt on the next act()
         return d.get("infos")
 
-    def get_inference_policy(self, device=None, fused: bool = False):
-        """The deterministic student: student observation -> action mean.  ``fused=True``: policy.FusedMLP([student]),
-        or for a recurrent student policy.RecurrentPolicy(memory_s.rnn, student, fused=True), which keeps its own
-        memory (reset the rows of finished episodes with the returned callable's ``reset(dones)``; on the torch path
-        with the policy module's)."""
-        self.eval_mode()
-        p = self.alg.policy
-        if device is not None:
-            p.to(device)
-            if self.empirical_normalization:
-                self.obs_normalizer.to(device)
-        norm = self.obs_normalizer if self.empirical_normalization else None
-        if p.is_recurrent:
-            if fused:
-                from .policy import RecurrentPolicy
-
-                return RecurrentPolicy(p.memory_s.rnn, p.student, norm, fused=True)
-            p.reset()
-            return p.act_inference
-        if fused:
-            from .policy import FusedMLP
-
-            f = FusedMLP([p.student], norm)
-            return lambda x: f(x)[0]
-        if norm is not None:
-            return lambda x: p.act_inference(norm(x))
-        return p.act_inference
-
-    def train_mode(self):
-        self.alg.policy.train()
-        if self.empirical_normalization:
-            self.obs_normalizer.train()
-
-    def eval_mode(self):
-        self.alg.policy.eval()
-        if self.empirical_normalization:
-            self.obs_normalizer.eval()
+    def _mode_modules(self) -> list:
+        return [self.alg.policy, self.obs_normalizer]  # not the teacher's normaliser: it stays in eval mode

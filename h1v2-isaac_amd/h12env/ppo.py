@@ -483,7 +483,39 @@ def enable_tunable_gemm():
         t.tuning_enable(True)
 
 
-class PPO:
+class _DeviceLrAdam:
+    """The optimizer of PPO and of h12env.distill.Distillation: Adam over ``self.policy``'s parameters."""
+
+    def _init_optimizer(self, learning_rate) -> bool:
+        """fused Adam (one kernel for all parameters) on the GPU with the learning rate as a device tensor, so
+        the KL-adaptive schedule runs on the device (no host sync per minibatch); plain Adam on CPU.  Returns whether
+        it is the fused one."""
+        fused = str(self.device).startswith("cuda")
+        self._lr_t = torch.tensor(float(learning_rate), device=self.device) if fused else None
+        self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
+                                          fused=fused, capturable=fused)
+        self.learning_rate = learning_rate
+        return fused
+
+    def optimizer_state_dict(self) -> dict:
+        """The optimizer state with a plain-float learning rate (rsl_rl's checkpoint layout)."""
+        sd = self.optimizer.state_dict()
+        for g in sd["param_groups"]:
+            if torch.is_tensor(g["lr"]):
+                g["lr"] = float(g["lr"])
+        return sd
+
+    def load_optimizer_state_dict(self, sd: dict):
+        self.optimizer.load_state_dict(sd)
+        lr = float(self.optimizer.param_groups[0]["lr"])
+        self.learning_rate = lr
+        if self._lr_t is not None:  # keep the device tensor the schedule updates in the param groups
+            self._lr_t.fill_(lr)
+            for g in self.optimizer.param_groups:
+                g["lr"] = self._lr_t
+
+
+class PPO(_DeviceLrAdam):
     """Clipped-surrogate PPO with clipped value loss, entropy bonus and KL-adaptive learning rate
     (rsl_rl 2.3 algorithms/ppo.py semantics)."""
 
@@ -498,15 +530,9 @@ class PPO:
         self.device = device
         if str(device).startswith("cuda") and os.environ.get("H12_TUNABLEOP", "0") == "1":
             enable_tunable_gemm()
-        # fused Adam (one kernel for all parameters) on the GPU with the learning rate as a device tensor, so
-        # the KL-adaptive schedule runs on the device (no host sync per minibatch); plain Adam on CPU
-        fused = str(device).startswith("cuda")
-        self._lr_t = torch.tensor(float(learning_rate), device=device) if fused else None
-        self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
-                                          fused=fused, capturable=fused)
+        fused = self._init_optimizer(learning_rate)
         self._graph = None
         self._fused = None
-        self.learning_rate = learning_rate
         self.num_learning_epochs = num_learning_epochs
         self.num_mini_batches = num_mini_batches
         self.clip_param = clip_param
@@ -1056,23 +1082,9 @@ class PPO:
                 self.rnd_fused.dirty = True  # the predictor moved: re-pack before the next collection step
         return out
 
-    def optimizer_state_dict(self) -> dict:
-        """The optimizer state with a plain-float learning rate (rsl_rl's checkpoint layout)."""
-        sd = self.optimizer.state_dict()
-        for g in sd["param_groups"]:
-            if torch.is_tensor(g["lr"]):
-                g["lr"] = float(g["lr"])
-        return sd
-
     def load_optimizer_state_dict(self, sd: dict):
-        self.optimizer.load_state_dict(sd)
+        super().load_optimizer_state_dict(sd)
         self._graph = None  # the captured graph holds the old state tensors
-        lr = float(self.optimizer.param_groups[0]["lr"])
-        self.learning_rate = lr
-        if self._lr_t is not None:  # keep the device tensor the schedule updates in the param groups
-            self._lr_t.fill_(lr)
-            for g in self.optimizer.param_groups:
-                g["lr"] = self._lr_t
 
     def broadcast_parameters(self):
         if self.shard.world > 1:
@@ -1104,9 +1116,53 @@ class _Logger:
             self._fh = None
 
 
+class EpisodeStats:
+    """rsl_rl's rewbuffer / lenbuffer: the reward sums and the lengths of the last 100 finished episodes, as
+    ``buffers[stream]`` and ``buffers["length"]``, one deque per named reward stream.
+
+    rsl_rl extends the deques at every step (a host sync per step); here ``step`` records the finished episodes on
+    the device and ``flush`` moves them once per iteration, in the same order (step-major, env index within a
+    step)."""
+
+    def __init__(self, num_envs: int, device, streams=("reward",)):
+        self.running = {k: torch.zeros(num_envs, device=device) for k in (*streams, "length")}
+        self.buffers = {k: deque(maxlen=100) for k in self.running}
+        self._done: list = []
+        self._at_done = {k: [] for k in self.running}
+
+    def step(self, dones, **rewards):
+        """One env step: ``rewards[stream]`` [num_envs] for every stream, ``dones`` [num_envs].  Device work only."""
+        for k, r in rewards.items():
+            self.running[k] += r
+        self.running["length"] += 1
+        done = dones > 0
+        self._done.append(done)
+        for k, cur in self.running.items():
+            self._at_done[k].append(torch.where(done, cur, 0.0))
+            cur.masked_fill_(done, 0.0)
+
+    def flush(self):
+        """The episodes finished since the last flush go into the deques: one mask, then one indexed transfer per
+        stream."""
+        if not self._done:
+            return
+        m = torch.stack(self._done)
+        self._done.clear()
+        for k, rows in self._at_done.items():
+            self.buffers[k].extend(torch.stack(rows)[m].cpu().tolist())
+            rows.clear()
+
+
 class OnPolicyRunner:
     """rsl_rl 2.3 OnPolicyRunner: collect num_steps_per_env transitions from every env, PPO update,
-    log, checkpoint every save_interval iterations."""
+    log, checkpoint every save_interval iterations.
+
+    h12env.distill.DistillationRunner is this runner around another algorithm.  What differs is in the methods after
+    ``__init__``: ``_build_algorithm``, the four steps of ``learn`` (``_check_ready``, ``_first_inputs``,
+    ``_step_inputs``, ``_end_collection``), ``_checkpoint_extras``, ``load``, ``_loss_scalars`` and the module names
+    below."""
+
+    _inference_modules = ("memory_a", "actor")  # of alg.policy: what get_inference_policy serves (memory: if recurrent)
 
     def __new__(cls, env=None, train_cfg: dict | None = None, *args, **kwargs):
         # algorithm.class_name = "Distillation" (with a StudentTeacher* policy) is served by h12env.distill's runner:
@@ -1130,6 +1186,27 @@ class OnPolicyRunner:
         # The env's own streams stay keyed by the global env id (shard-invariant trajectories).
         seed = int(train_cfg.get("seed", 1))
         torch.manual_seed(seed + self.shard.rank)
+        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
+        self.save_interval = int(train_cfg.get("save_interval", 50))
+        self.empirical_normalization = bool(train_cfg.get("empirical_normalization", False))
+        self._build_algorithm()
+        self.log_dir = log_dir
+        self.logger = _Logger(log_dir, self.shard.rank)
+        self.tot_timesteps = 0
+        self.tot_time = 0.0
+        self.current_learning_iteration = 0
+        self.git_status_repos: list[str] = []
+        self.last_iteration_stats: dict = {}
+        self.env.reset()
+
+    def _normalizer(self, width: int) -> nn.Module:
+        if self.empirical_normalization:
+            return EmpiricalNormalization([width], until=1.0e8).to(self.device)
+        return nn.Identity().to(self.device)
+
+    def _build_algorithm(self):
+        """self.alg with its storage, and the two observation normalisers."""
+        env, device = self.env, self.device
         obs, extras = env.get_observations()
         num_obs = obs.shape[1]
         critic_obs = extras["observations"].get("critic")
@@ -1150,52 +1227,45 @@ class OnPolicyRunner:
             self.alg_cfg["symmetry_cfg"] = {**self.alg_cfg["symmetry_cfg"], "_env": env}
         self.alg = PPO(policy, device=device, shard=self.shard, **self.alg_cfg)
         self.alg.broadcast_parameters()
-        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
-        self.save_interval = int(train_cfg.get("save_interval", 50))
-        self.empirical_normalization = bool(train_cfg.get("empirical_normalization", False))
-        if self.empirical_normalization:
-            self.obs_normalizer = EmpiricalNormalization([num_obs], until=1.0e8).to(device)
-            self.critic_obs_normalizer = EmpiricalNormalization([num_critic_obs], until=1.0e8).to(device)
-        else:
-            self.obs_normalizer = nn.Identity().to(device)
-            self.critic_obs_normalizer = nn.Identity().to(device)
+        self.obs_normalizer = self._normalizer(num_obs)
+        self.critic_obs_normalizer = self._normalizer(num_critic_obs)
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [num_obs],
                               None if critic_obs is None else [num_critic_obs], [env.num_actions])
-        self.log_dir = log_dir
-        self.logger = _Logger(log_dir, self.shard.rank)
-        self.tot_timesteps = 0
-        self.tot_time = 0.0
-        self.current_learning_iteration = 0
-        self.git_status_repos: list[str] = []
-        self.last_iteration_stats: dict = {}
-        self.env.reset()
+
+    # ---- the steps of learn() that depend on the algorithm
+    def _check_ready(self):
+        pass
+
+    def _first_inputs(self):
+        """alg.act's two inputs at the first step of learn(): the env's observations as they are (not normalised)."""
+        obs, extras = self.env.get_observations()
+        critic_obs = extras["observations"].get("critic", obs)
+        return obs.to(self.device), critic_obs.to(self.device)
+
+    def _step_inputs(self, obs, infos):
+        """alg.act's two inputs for the next step, from env.step's (obs, infos)."""
+        obs = self.obs_normalizer(obs.to(self.device))
+        critic_obs = infos["observations"].get("critic", obs)
+        return obs, self.critic_obs_normalizer(critic_obs.to(self.device))
+
+    def _end_collection(self, critic_obs):
+        """Between the last env step and alg.update(); counted as learning time."""
+        self.alg.compute_returns(critic_obs)
 
     # ---- API used by train.py / play.py
     def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False):
+        self._check_ready()
         if init_at_random_ep_len:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf,
                                                              high=int(self.env.max_episode_length))
-        obs, extras = self.env.get_observations()
-        critic_obs = extras["observations"].get("critic", obs)
-        obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
+        obs, critic_obs = self._first_inputs()
         self.train_mode()
         self._store_git_state()
         ep_infos: list[dict] = []
-        rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
-        cur_reward_sum = torch.zeros(self.env.num_envs, device=self.device)
-        cur_episode_length = torch.zeros(self.env.num_envs, device=self.device)
-        done_mask: list = []
-        done_rew: list = []
-        done_len: list = []
-        rnd = getattr(self.alg, "rnd", None) is not None  # extrinsic / intrinsic episode sums, collected as rewbuffer is
-        if rnd:
-            erewbuffer, irewbuffer = deque(maxlen=100), deque(maxlen=100)
-            cur_ereward_sum = torch.zeros(self.env.num_envs, device=self.device)
-            cur_ireward_sum = torch.zeros(self.env.num_envs, device=self.device)
-            done_erew: list = []
-            done_irew: list = []
+        rnd = self.alg.rnd is not None  # extrinsic / intrinsic episode sums, collected as the reward's are
+        episodes = EpisodeStats(self.env.num_envs, self.device,
+                                ("reward", "extrinsic", "intrinsic") if rnd else ("reward",))
         start_iter = self.current_learning_iteration
-        self._start_iter = start_iter
         tot_iter = start_iter + num_learning_iterations
         for it in range(start_iter, tot_iter):
             start = time.time()
@@ -1203,60 +1273,30 @@ class OnPolicyRunner:
                 for _ in range(self.num_steps_per_env):
                     actions = self.alg.act(obs, critic_obs)
                     obs, rewards, dones, infos = self.env.step(actions.to(self.env.device))
-                    obs, rewards, dones = obs.to(self.device), rewards.to(self.device), dones.to(self.device)
-                    obs = self.obs_normalizer(obs)
-                    critic_obs = infos["observations"].get("critic", obs)
-                    critic_obs = self.critic_obs_normalizer(critic_obs.to(self.device))
+                    rewards, dones = rewards.to(self.device), dones.to(self.device)
+                    obs, critic_obs = self._step_inputs(obs, infos)
                     self.alg.process_env_step(rewards, dones, infos)
                     if self.log_dir is not None:
                         if "episode" in infos:
                             ep_infos.append(infos["episode"])
                         elif "log" in infos:
                             ep_infos.append(infos["log"])
-                        # rsl_rl extends the reward / length deques at every step (a host sync per step);
-                        # the finished episodes are recorded on the device and moved once per iteration,
-                        # in the same order (step-major, env index within a step)
                         if rnd:  # rsl_rl: the logged reward is extrinsic + intrinsic
                             intrinsic = self.alg.intrinsic_rewards
-                            cur_ereward_sum += rewards
-                            cur_ireward_sum += intrinsic
-                            cur_reward_sum += rewards + intrinsic
+                            episodes.step(dones, reward=rewards + intrinsic, extrinsic=rewards, intrinsic=intrinsic)
                         else:
-                            cur_reward_sum += rewards
-                        cur_episode_length += 1
-                        done = dones > 0
-                        done_mask.append(done)
-                        done_rew.append(torch.where(done, cur_reward_sum, 0.0))
-                        done_len.append(torch.where(done, cur_episode_length, 0.0))
-                        cur_reward_sum.masked_fill_(done, 0.0)
-                        cur_episode_length.masked_fill_(done, 0.0)
-                        if rnd:
-                            done_erew.append(torch.where(done, cur_ereward_sum, 0.0))
-                            done_irew.append(torch.where(done, cur_ireward_sum, 0.0))
-                            cur_ereward_sum.masked_fill_(done, 0.0)
-                            cur_ireward_sum.masked_fill_(done, 0.0)
-                if self.log_dir is not None and done_mask:
-                    m = torch.stack(done_mask)
-                    rewbuffer.extend(torch.stack(done_rew)[m].cpu().tolist())
-                    lenbuffer.extend(torch.stack(done_len)[m].cpu().tolist())
-                    if rnd:
-                        erewbuffer.extend(torch.stack(done_erew)[m].cpu().tolist())
-                        irewbuffer.extend(torch.stack(done_irew)[m].cpu().tolist())
-                        done_erew.clear()
-                        done_irew.clear()
-                    done_mask.clear()
-                    done_rew.clear()
-                    done_len.clear()
+                            episodes.step(dones, reward=rewards)
+                if self.log_dir is not None:
+                    episodes.flush()
                 stop = time.time()
                 collection_time = stop - start
                 start = stop
-                self.alg.compute_returns(critic_obs)
+                self._end_collection(critic_obs)
             loss = self.alg.update()
             stop = time.time()
             learn_time = stop - start
             self.current_learning_iteration = it
-            self._rnd_buffers = (erewbuffer, irewbuffer) if rnd else None
-            self._log(it, tot_iter, collection_time, learn_time, loss, ep_infos, rewbuffer, lenbuffer)
+            self._log(it, start_iter, tot_iter, collection_time, learn_time, loss, ep_infos, episodes.buffers)
             if self.log_dir is not None and it % self.save_interval == 0:
                 self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
             ep_infos.clear()
@@ -1264,7 +1304,7 @@ class OnPolicyRunner:
         if self.log_dir is not None:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
 
-    def _log(self, it, tot_iter, collection_time, learn_time, loss, ep_infos, rewbuffer, lenbuffer):
+    def _log(self, it, start_iter, tot_iter, collection_time, learn_time, loss, ep_infos, episodes):
         steps = self.num_steps_per_env * self.env.num_envs * self.shard.world
         self.tot_timesteps += steps
         it_time = collection_time + learn_time
@@ -1281,15 +1321,14 @@ class OnPolicyRunner:
             vals = [float(torch.as_tensor(e[key]).float().mean()) for e in ep_infos if key in e]
             if vals:
                 scalars[key if "/" in key else "Episode/" + key] = sum(vals) / len(vals)
-        if rewbuffer:
-            scalars["Train/mean_reward"] = statistics.mean(rewbuffer)
-            scalars["Train/mean_episode_length"] = statistics.mean(lenbuffer)
-        if getattr(self.alg, "rnd", None) is not None:
+        if episodes["reward"]:
+            scalars["Train/mean_reward"] = statistics.mean(episodes["reward"])
+            scalars["Train/mean_episode_length"] = statistics.mean(episodes["length"])
+        if self.alg.rnd is not None:
             scalars["Rnd/weight"] = self.alg.rnd.weight
-            ebuf, ibuf = getattr(self, "_rnd_buffers", None) or ((), ())
-            if ebuf:
-                scalars["Rnd/mean_extrinsic_reward"] = statistics.mean(ebuf)
-                scalars["Rnd/mean_intrinsic_reward"] = statistics.mean(ibuf)
+            if episodes["extrinsic"]:
+                scalars["Rnd/mean_extrinsic_reward"] = statistics.mean(episodes["extrinsic"])
+                scalars["Rnd/mean_intrinsic_reward"] = statistics.mean(episodes["intrinsic"])
         self.last_iteration_stats = scalars
         if self.shard.rank != 0:
             return
@@ -1300,7 +1339,7 @@ class OnPolicyRunner:
         for k, v in scalars.items():
             if not k.startswith("Perf/"):
                 lines.append(f"{k + ':':>35} {v:.4f}")
-        eta = self.tot_time / max(1, it + 1 - self._start_iter) * (tot_iter - it - 1)
+        eta = self.tot_time / max(1, it + 1 - start_iter) * (tot_iter - it - 1)
         lines += [f"{'-' * width}", f"{'Total timesteps:':>35} {self.tot_timesteps}",
                   f"{'Iteration time:':>35} {it_time:.2f}s", f"{'Total time:':>35} {self.tot_time:.2f}s",
                   f"{'ETA:':>35} {eta:.1f}s"]
@@ -1319,11 +1358,18 @@ class OnPolicyRunner:
              "iter": self.current_learning_iteration, "infos": infos}
         if self.empirical_normalization:
             d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+        d.update(self._checkpoint_extras())
+        torch.save(d, path)
+
+    def _checkpoint_extras(self) -> dict:
+        """The checkpoint's keys beyond the model, the optimizer and the observation normaliser."""
+        d = {}
+        if self.empirical_normalization:
             d["critic_obs_norm_state_dict"] = self.critic_obs_normalizer.state_dict()
-        if getattr(self.alg, "rnd", None) is not None:
+        if self.alg.rnd is not None:
             d["rnd_state_dict"] = self.alg.rnd.rnd_state_dict()
             d["rnd_optimizer_state_dict"] = self.alg.rnd_optimizer.state_dict()
-        torch.save(d, path)
+        return d
 
     def load(self, path: str, load_optimizer: bool = True):
         d = torch.load(path, map_location=self.device, weights_only=True)
@@ -1337,11 +1383,11 @@ class OnPolicyRunner:
             raise ValueError(f"{path}: the checkpoint's critic reads {w.shape[1]}-wide observations, this env's "
                              f"critic observation is {mine} wide -- the two were built with different "
                              "--privileged_critic settings (env.observations.critic)")
-        if getattr(self.alg, "rnd", None) is not None and "rnd_state_dict" not in d:
+        if self.alg.rnd is not None and "rnd_state_dict" not in d:
             raise ValueError(f"{path}: the checkpoint holds no rnd_state_dict, this run trains with rnd_cfg -- resume it "
                              "without rnd_cfg, or start the RND run afresh")
         self.alg.policy.load_state_dict(d["model_state_dict"])
-        if getattr(self.alg, "rnd", None) is not None:
+        if self.alg.rnd is not None:
             self.alg.rnd.load_rnd_state_dict(d["rnd_state_dict"])
             if load_optimizer and "rnd_optimizer_state_dict" in d:
                 self.alg.rnd_optimizer.load_state_dict(d["rnd_optimizer_state_dict"])
@@ -1358,57 +1404,48 @@ class OnPolicyRunner:
         return d.get("infos")
 
     def get_inference_policy(self, device=None, fused: bool = False):
-        """The deterministic policy obs -> action mean.  ``fused=True``: one h12learn_mlp_forward launch (normaliser +
+        """The deterministic policy obs -> action mean (DistillationRunner: the student's, from the student
+        observation).  ``fused=True``: one h12learn_mlp_forward launch (normaliser +
         actor, h12env.policy.FusedMLP) packed from the parameters as they are now; the default is the torch path.
 
         A recurrent policy's is stateful: it starts from an empty memory, and the caller resets the rows of finished
         episodes (``policy.reset(dones)``: the returned callable's own ``reset`` with ``fused``, the policy module's
         otherwise).  ``fused=True``: h12env.policy.RecurrentPolicy on h12learn_lstm_step."""
         self.eval_mode()
+        p = self.alg.policy
+        memory, net = (getattr(p, name, None) for name in self._inference_modules)
+        norm = self.obs_normalizer if self.empirical_normalization else None
         if device is not None:
-            self.alg.policy.to(device)
-        if self.alg.policy.is_recurrent:
-            norm = self.obs_normalizer if self.empirical_normalization else None
-            if norm is not None and device is not None:
+            p.to(device)
+            if norm is not None:
                 norm.to(device)
+        if p.is_recurrent:
             if fused:
                 from .policy import RecurrentPolicy
 
-                return RecurrentPolicy(self.alg.policy.memory_a.rnn, self.alg.policy.actor, norm, fused=True)
-            self.alg.policy.reset()
-            if norm is not None:
-                return lambda x: self.alg.policy.act_inference(norm(x))
-            return self.alg.policy.act_inference
-        if fused:
+                return RecurrentPolicy(memory.rnn, net, norm, fused=True)
+            p.reset()
+        elif fused:
             from .policy import FusedMLP
 
-            if device is not None and self.empirical_normalization:
-                self.obs_normalizer.to(device)
-            f = FusedMLP([self.alg.policy.actor], self.obs_normalizer if self.empirical_normalization else None)
+            f = FusedMLP([net], norm)
             return lambda x: f(x)[0]
-        policy = self.alg.policy.act_inference
-        if self.empirical_normalization:
-            if device is not None:
-                self.obs_normalizer.to(device)
-            norm = self.obs_normalizer
-            return lambda x: self.alg.policy.act_inference(norm(x))
-        return policy
+        if norm is not None:
+            return lambda x: p.act_inference(norm(x))
+        return p.act_inference
+
+    def _mode_modules(self) -> list:
+        """What train_mode() / eval_mode() switch."""
+        return [self.alg.policy, self.obs_normalizer, self.critic_obs_normalizer,
+                *([] if self.alg.rnd is None else [self.alg.rnd])]
 
     def train_mode(self):
-        self.alg.policy.train()
-        if getattr(self.alg, "rnd", None) is not None:
-            self.alg.rnd.train()
-        if self.empirical_normalization:
-            self.obs_normalizer.train()
-            self.critic_obs_normalizer.train()
+        for m in self._mode_modules():
+            m.train()
 
     def eval_mode(self):
-        self.alg.policy.eval()
-        if getattr(self.alg, "rnd", None) is not None:
-            self.alg.rnd.eval()
-        if self.empirical_normalization:
-            self.obs_normalizer.eval()
-            self.critic_obs_normalizer.eval()
+        for m in self._mode_modules():
+            m.eval()
 
     def add_git_repo_to_log(self, repo_file_path):
         self.git_status_repos.append(repo_file_path)

@@ -20,7 +20,8 @@ LEARN_SYMBOLS = ["h12learn_rms_row_chunk", "h12learn_rms_workspace_bytes", "h12l
                  "h12learn_cleanrl_head", "h12learn_lstm_max_hidden", "h12learn_lstm_packed_bytes",
                  "h12learn_lstm_pack", "h12learn_lstm_step", "h12learn_lstm_seq_packed_bytes",
                  "h12learn_lstm_seq_pack", "h12learn_lstm_seq_forward", "h12learn_lstm_seq_backward",
-                 "h12learn_rnd_reward", "h12learn_rnd_finish", "h12learn_last_error"]
+                 "h12learn_rnd_reward", "h12learn_rnd_finish", "h12learn_optim_chunk", "h12learn_optim_max_tensors",
+                 "h12learn_optim_fold", "h12learn_optim_workspace_bytes", "h12learn_optim_step", "h12learn_last_error"]
 
 MLP_MAX_NETS = 4
 MLP_MAX_LAYERS = 8
@@ -119,6 +120,19 @@ class RndFinishArgs(C.Structure):
                 ("first", C.c_void_p), ("intrinsic", C.c_void_p), ("total", C.c_void_p)]
 
 
+OPTIM_ADAM, OPTIM_RADAM = 0, 1
+
+
+class OptimArgs(C.Structure):
+    """h12learn_optim_args"""
+    _fields_ = [("rule", C.c_int), ("n_tensors", C.c_int), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("max_norm", C.c_double), ("lr", C.c_double), ("lr_dev", C.c_void_p),
+                ("p", C.POINTER(C.c_void_p)), ("g", C.POINTER(C.c_void_p)), ("exp_avg", C.POINTER(C.c_void_p)),
+                ("exp_avg_sq", C.POINTER(C.c_void_p)), ("step", C.POINTER(C.c_void_p)),
+                ("numel", C.POINTER(C.c_longlong)), ("grad_norm", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 _bound = None
 
 
@@ -200,6 +214,13 @@ def learn_library():
     lib.h12learn_rnd_reward.restype = C.c_int
     lib.h12learn_rnd_finish.argtypes = [C.POINTER(RndFinishArgs), vp]
     lib.h12learn_rnd_finish.restype = C.c_int
+    for q in ("h12learn_optim_chunk", "h12learn_optim_max_tensors", "h12learn_optim_fold"):
+        getattr(lib, q).argtypes = []
+        getattr(lib, q).restype = C.c_int
+    lib.h12learn_optim_workspace_bytes.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+    lib.h12learn_optim_workspace_bytes.restype = C.c_size_t
+    lib.h12learn_optim_step.argtypes = [C.POINTER(OptimArgs), vp]
+    lib.h12learn_optim_step.restype = C.c_int
     lib.h12learn_last_error.argtypes = []
     lib.h12learn_last_error.restype = C.c_char_p
     _bound = lib
@@ -792,8 +813,6 @@ def cleanrl_head(mean: torch.Tensor, value: torch.Tensor, logstd: torch.Tensor, 
     return outputs
 
 
-
-
 # ---- Random Network Distillation's reward step (csrc/h12_rnd.hip)
 def rnd_reward(desc: MlpDesc, packed: torch.Tensor, x: torch.Tensor, err: torch.Tensor | None = None,
                xn: torch.Tensor | None = None, emb: bool = False):
@@ -827,3 +846,68 @@ def rnd_finish(args: RndFinishArgs, device):
     caller fills ``args`` with the data pointers of tensors it keeps alive."""
     lib = learn_library()
     _check(lib, lib.h12learn_rnd_finish(C.byref(args), _stream(device)), "h12learn_rnd_finish")
+
+
+# ---- fused optimiser step (csrc/h12_optim.hip): gradient clip + Adam / RAdam of every tensor in two launches
+def optim_chunk() -> int:
+    return learn_library().h12learn_optim_chunk()
+
+
+def optim_max_tensors() -> int:
+    return learn_library().h12learn_optim_max_tensors()
+
+
+def optim_fold() -> int:
+    return learn_library().h12learn_optim_fold()
+
+
+def optim_workspace_bytes(numels) -> int:
+    lib = learn_library()
+    numels = [int(n) for n in numels]
+    nbytes = lib.h12learn_optim_workspace_bytes((C.c_longlong * max(1, len(numels)))(*numels), len(numels))
+    if nbytes == 0:
+        _check(lib, -1, "h12learn_optim_workspace_bytes")
+    return nbytes
+
+
+def optim_step(rule: int, params, grads, exp_avgs, exp_avg_sqs, steps, beta1: float, beta2: float, eps: float,
+               max_norm: float | None, lr, workspace: torch.Tensor, grad_norm: torch.Tensor | None = None):
+    """Two launches (h12learn_optim_step): the global norm of ``grads``, then the clip coefficient and the Adam
+    (OPTIM_ADAM) or RAdam (OPTIM_RADAM) update of every tensor of ``params`` with its moments, in place.  ``steps``: one
+    float32 device scalar per tensor, incremented by the call.  ``lr``: a float, or a float32 device scalar the kernel
+    reads.  ``max_norm``: None or <= 0 for no clip.  ``grad_norm`` (a float32 device scalar) receives the norm.
+    ``workspace``: at least optim_workspace_bytes of the tensors' sizes.  The gradients are not rescaled in memory."""
+    lib = learn_library()
+    n = len(params)
+    if not (n >= 1 and len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
+        raise ValueError(f"optim_step: {n} parameters, {len(grads)} gradients, {len(exp_avgs)} / {len(exp_avg_sqs)} "
+                         f"moments, {len(steps)} steps")
+    for i in range(n):
+        numel = params[i].numel()
+        for name, t in (("params", params[i]), ("grads", grads[i]), ("exp_avgs", exp_avgs[i]),
+                        ("exp_avg_sqs", exp_avg_sqs[i])):
+            if _f32(t, f"{name}[{i}]").numel() != numel or numel < 1:
+                raise ValueError(f"optim_step: {name}[{i}] has {t.numel()} elements, params[{i}] {numel} (>= 1)")
+        if _f32(steps[i], f"steps[{i}]").numel() != 1:
+            raise ValueError(f"optim_step: steps[{i}] must be one float32 element")
+    if not (workspace.is_cuda and workspace.is_contiguous()):
+        raise ValueError("optim_step: workspace must be a contiguous CUDA tensor")
+    a = OptimArgs()
+    a.rule, a.n_tensors = int(rule), n
+    a.beta1, a.beta2, a.eps = float(beta1), float(beta2), float(eps)
+    a.max_norm = 0.0 if max_norm is None else float(max_norm)
+    if torch.is_tensor(lr):
+        if _f32(lr, "lr").numel() != 1:
+            raise ValueError("optim_step: a tensor lr must be one float32 element")
+        a.lr, a.lr_dev = 0.0, lr.data_ptr()
+    else:
+        a.lr = float(lr)
+    ptrs = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
+    a.p, a.g, a.exp_avg, a.exp_avg_sq, a.step = ptrs(params), ptrs(grads), ptrs(exp_avgs), ptrs(exp_avg_sqs), ptrs(steps)
+    a.numel = (C.c_longlong * n)(*[p.numel() for p in params])
+    if grad_norm is not None:
+        if _f32(grad_norm, "grad_norm").numel() != 1:
+            raise ValueError("optim_step: grad_norm must be one float32 element")
+        a.grad_norm = grad_norm.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    _check(lib, lib.h12learn_optim_step(C.byref(a), _stream(params[0].device)), "h12learn_optim_step")

@@ -28,7 +28,7 @@ def hipcc() -> str:
 # the translation units of libh12env.so, in link order
 UNITS = [CSRC / n for n in ("h12env.hip", "h12_learn.hip", "h12_policy.hip", "h12_policy_train.hip",
                             "h12_policy_rnn.hip", "h12_policy_rnn_train.hip", "h12_ppo_head.hip", "h12_priv.hip",
-                            "h12_student.hip", "h12_rnd.hip", "h12_render.hip")]
+                            "h12_student.hip", "h12_rnd.hip", "h12_optim.hip", "h12_render.hip")]
 # -fno-slp-vectorize: packed-fp32 SLP code needs register pairs and costs ~30 % extra v_mov here.
 # -ffinite-math-only -fno-signed-zeros: the state is finite by construction, so products with
 # the model's zero constants fold away and fminf/fmaxf need no NaN canonicalisation (-21 % VALU

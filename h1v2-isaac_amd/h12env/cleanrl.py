@@ -34,6 +34,9 @@ Deviations from the reference, all deliberate:
     capturable RAdam with the learning rate as a device scalar, and on CUDA a whole minibatch (gather, forwards, head,
     backward, gradient clip, RAdam step) replays as one HIP graph per minibatch size; ``H12_PPO_GRAPH=0`` runs the
     same minibatch eagerly, bit for bit;
+  * with ``fused_optimizer`` (``PPO(..., fused_optimizer=True)``, ``H12_OPTIMIZER_FUSED=1``, ``train_cleanrl.py
+    --fused_optimizer``) the gradient clip and the RAdam step of either update path are
+    ``h12env.optim.FusedClipRAdam``: two HIP launches on CUDA, ``clip_grad_norm_`` and torch's own rule on CPU;
   * the storage, the agent and the rollout live on the env's device (the reference picks cuda when available);
   * the running statistics are updated in place (the reference rebinds the buffers), so a graph can hold them;
   * ``PPO`` returns the trained agent (the reference returns None) and takes ``resume_path`` / ``on_step``.
@@ -357,8 +360,9 @@ class _FusedUpdate:
     first use (graphs.capture: the warm-up's changes to parameters, optimiser state and statistics are put back bit for
     bit).  On CPU the node evaluates the default path's expressions."""
 
-    def __init__(self, agent, optimizer, cfg, batch_size: int, device, graphed: bool):
+    def __init__(self, agent, optimizer, cfg, batch_size: int, device, graphed: bool, clip: bool = True):
         self.agent, self.optimizer, self.cfg, self.device = agent, optimizer, cfg, device
+        self.clip = clip  # False: the optimiser clips inside its step (optim.FusedClipRAdam)
         self.cuda = device.type == "cuda"
         self.graphed = graphed and self.cuda
         self._graphs: dict = {}  # minibatch size -> (graph, static index buffer)
@@ -391,7 +395,8 @@ class _FusedUpdate:
         loss, out = CleanRLHead.apply(agent.actor_mean(x), agent.critic(x), agent.actor_logstd, h)
         self.optimizer.zero_grad()
         loss.backward()
-        nn.utils.clip_grad_norm_(agent.parameters(), c.max_grad_norm)
+        if self.clip:
+            nn.utils.clip_grad_norm_(agent.parameters(), c.max_grad_norm)
         self.optimizer.step()
         return out
 
@@ -425,14 +430,18 @@ class _FusedUpdate:
 
 
 # ---------------------------------------------------------------------------------------------- PPO
-def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None, fused_loss: bool | None = None):
+def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None, fused_loss: bool | None = None,
+        fused_optimizer: bool | None = None):
     """biped_tasks/utils/cleanrl/ppo.py:121-369 (the module docstring lists the deviations).  ``on_step(step_index,
     obs, action, logprob, value)`` is a read-only observer of each stored transition (tests, probes).  ``fused_loss``
-    (None: ``H12_CLEANRL_HEAD_FUSED=1``) selects the fused loss head and, on CUDA, the captured update."""
+    (None: ``H12_CLEANRL_HEAD_FUSED=1``) selects the fused loss head and, on CUDA, the captured update;
+    ``fused_optimizer`` (None: ``H12_OPTIMIZER_FUSED=1``) selects optim.FusedClipRAdam, clip included, on both."""
+    from .optim import FusedClipRAdam, fused_optimizer_enabled
     from .ppo import _Logger
     from .ppo_head import cleanrl_fused_loss_enabled
 
     fused_loss = cleanrl_fused_loss_enabled() if fused_loss is None else bool(fused_loss)
+    fused_optimizer = fused_optimizer_enabled() if fused_optimizer is None else bool(fused_optimizer)
 
     if ppo_cfg.logger == "wandb":
         raise RuntimeError("logger='wandb' is not available on this stack (no wandb package); use 'tensorboard', "
@@ -476,10 +485,18 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None, f
                                  f"{_learn.ppo_head_max_actions()}")
             # the learning rate as a device scalar: the annealing rewrites it under a captured step
             lr_t = torch.tensor(LEARNING_RATE, dtype=torch.float32, device=device)
-            optimizer = optim.RAdam(agent.parameters(), lr=lr_t, eps=1e-5, capturable=True)
+            if fused_optimizer:  # in place of the capturable RAdam inside the graph
+                optimizer = FusedClipRAdam(agent.parameters(), lr=lr_t, eps=1e-5, max_norm=MAX_GRAD_NORM)
+            else:
+                optimizer = optim.RAdam(agent.parameters(), lr=lr_t, eps=1e-5, capturable=True)
+        elif fused_optimizer:
+            optimizer = FusedClipRAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5, max_norm=MAX_GRAD_NORM)
         else:
             optimizer = optim.RAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5)
-        updater = _FusedUpdate(agent, optimizer, ppo_cfg, BATCH_SIZE, device, _graph_enabled(device))
+        updater = _FusedUpdate(agent, optimizer, ppo_cfg, BATCH_SIZE, device, _graph_enabled(device),
+                               clip=not fused_optimizer)
+    elif fused_optimizer:
+        optimizer = FusedClipRAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5, max_norm=MAX_GRAD_NORM)
     else:
         optimizer = optim.RAdam(agent.parameters(), lr=LEARNING_RATE, eps=1e-5)
     lr_host = LEARNING_RATE
@@ -590,7 +607,8 @@ def PPO(envs, ppo_cfg, run_path, resume_path: str | None = None, on_step=None, f
 
                 optimizer.zero_grad()
                 loss.backward()
-                nn.utils.clip_grad_norm_(agent.parameters(), MAX_GRAD_NORM)
+                if not fused_optimizer:
+                    nn.utils.clip_grad_norm_(agent.parameters(), MAX_GRAD_NORM)
                 optimizer.step()
 
         num_updates = UPDATES_EPOCHS * BATCH_SIZE / MINIBATCH_SIZE

@@ -486,14 +486,21 @@ def enable_tunable_gemm():
 class _DeviceLrAdam:
     """The optimizer of PPO and of h12env.distill.Distillation: Adam over ``self.policy``'s parameters."""
 
-    def _init_optimizer(self, learning_rate) -> bool:
+    def _init_optimizer(self, learning_rate, fused_optimizer: bool = False) -> bool:
         """fused Adam (one kernel for all parameters) on the GPU with the learning rate as a device tensor, so
         the KL-adaptive schedule runs on the device (no host sync per minibatch); plain Adam on CPU.  Returns whether
-        it is the fused one."""
+        it is the fused one.  ``fused_optimizer``: on the GPU, h12env.optim.FusedClipAdam instead, which clips to
+        ``self.max_grad_norm`` inside its step; ``self.fused_optimizer`` says whether it is in use."""
         fused = str(self.device).startswith("cuda")
         self._lr_t = torch.tensor(float(learning_rate), device=self.device) if fused else None
-        self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
-                                          fused=fused, capturable=fused)
+        self.fused_optimizer = bool(fused_optimizer) and fused
+        if self.fused_optimizer:
+            from .optim import FusedClipAdam
+
+            self.optimizer = FusedClipAdam(self.policy.parameters(), lr=self._lr_t, max_norm=self.max_grad_norm)
+        else:
+            self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=self._lr_t if fused else learning_rate,
+                                              fused=fused, capturable=fused)
         self.learning_rate = learning_rate
         return fused
 
@@ -524,13 +531,25 @@ class PPO(_DeviceLrAdam):
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
                  normalize_advantage_per_mini_batch=False, shard: D.Shard | None = None, precision: str = "fp32",
                  symmetry_cfg: dict | None = None, fused_learner: bool | None = None, fused_loss: bool | None = None,
-                 fused_rnn_update: bool | None = None, rnd_cfg: dict | None = None, **kwargs):
+                 fused_rnn_update: bool | None = None, rnd_cfg: dict | None = None,
+                 fused_optimizer: bool | None = None, **kwargs):
         self.policy = policy.to(device)
         self.actor_critic = self.policy  # rsl_rl < 2.3 name
         self.device = device
         if str(device).startswith("cuda") and os.environ.get("H12_TUNABLEOP", "0") == "1":
             enable_tunable_gemm()
-        fused = self._init_optimizer(learning_rate)
+        # opt-in: gradient clip and Adam step as two HIP launches (h12env.optim.FusedClipAdam) on the GPU;
+        # _minibatch then leaves its clip_grad_norm_ call out.  None reads H12_OPTIMIZER_FUSED=1.  The default stays
+        # torch's clip and fused Adam.  Distillation and the RND predictor keep torch's Adam.
+        if fused_optimizer is None:
+            from .optim import fused_optimizer_enabled
+
+            fused_optimizer = fused_optimizer_enabled()
+        if fused_optimizer and shard is not None and shard.world > 1:
+            raise ValueError("fused_optimizer with more than one rank is not supported (the gradients are averaged "
+                             "across ranks between backward and the clip)")
+        self.max_grad_norm = max_grad_norm
+        fused = self._init_optimizer(learning_rate, fused_optimizer)
         self._graph = None
         self._fused = None
         self.num_learning_epochs = num_learning_epochs
@@ -947,7 +966,8 @@ class PPO(_DeviceLrAdam):
         self.optimizer.zero_grad(set_to_none=True)  # backward writes the grads (no fill + add)
         loss.backward()
         self._allreduce_grads()
-        nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        if not self.fused_optimizer:  # FusedClipAdam clips inside its step
+            nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         self.optimizer.step()
         if self.rnd is not None:  # the predictor's own loss, backward and Adam, after the policy's
             s_b = b["rnd_state"][idx]

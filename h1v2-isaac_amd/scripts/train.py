@@ -73,6 +73,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused_loss", action="store_true", default=False,
                     help="the PPO update's loss head (gathers, losses, gradients, KL schedule) as one fused HIP call "
                          "(h12env.ppo_head.PPOHead; agent.algorithm.fused_loss=true works too)")
+    ap.add_argument("--fused_optimizer", action="store_true", default=False,
+                    help="the PPO update's gradient clip and Adam step as two fused HIP launches "
+                         "(h12env.optim.FusedClipAdam; agent.algorithm.fused_optimizer=true works too)")
     rnd = ap.add_argument_group("rnd", "rsl_rl's rnd_cfg: Random Network Distillation, an exploration bonus (h12env.rnd)")
     rnd.add_argument("--rnd", action="store_true", default=False,
                      help="add RND's intrinsic reward: sets env.observations.rnd_state (the defaults of RndStateObsCfg) and "
@@ -110,7 +113,7 @@ def make_distillation(agent_cfg, env_cfg, args):
     from isaaclab_rl.rsl_rl import (RslRlDistillationAlgorithmCfg, RslRlDistillationStudentTeacherCfg,
                                     RslRlDistillationStudentTeacherRecurrentCfg)
 
-    for flag in ("symmetry", "fused_learner", "fused_loss", "recurrent", "rnd", "rnd_fused"):
+    for flag in ("symmetry", "fused_learner", "fused_loss", "fused_optimizer", "recurrent", "rnd", "rnd_fused"):
         if getattr(args, flag, None):
             raise SystemExit(f"--distill does not take --{flag} (a PPO option; the student's memory is --student_recurrent)")
     if not args.teacher_checkpoint and not args.resume:
@@ -214,6 +217,8 @@ def apply_cli(agent_cfg, env_cfg, args):
         agent_cfg.algorithm.fused_loss = True
     if getattr(args, "fused_rnn_update", False):
         agent_cfg.algorithm.fused_rnn_update = True
+    if getattr(args, "fused_optimizer", False):
+        agent_cfg.algorithm.fused_optimizer = True
     r = getattr(agent_cfg.algorithm, "rnd_cfg", None)
     if getattr(args, "rnd_fused", False):
         if r is None:

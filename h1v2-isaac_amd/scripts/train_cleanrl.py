@@ -67,6 +67,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_iterations", type=int, default=None)
     ap.add_argument("--fused_loss", action="store_true", default=False,
                     help="fused loss head (h12learn_cleanrl_head) and, on the GPU, the update as a captured graph")
+    ap.add_argument("--fused_optimizer", action="store_true", default=False,
+                    help="gradient clip and RAdam step as two fused HIP launches (h12env.optim.FusedClipRAdam)")
     add_clean_rl_args(ap)
     AppLauncher.add_app_launcher_args(ap)
     return ap
@@ -126,7 +128,8 @@ def main(argv=None) -> int:
         print_dict(vk, nesting=4)
         env = gym.wrappers.RecordVideo(env, **vk)
 
-    PPO(env, agent_cfg, log_dir, resume_path=resume_path, fused_loss=True if args.fused_loss else None)
+    PPO(env, agent_cfg, log_dir, resume_path=resume_path, fused_loss=True if args.fused_loss else None,
+        fused_optimizer=True if args.fused_optimizer else None)
     env.close()
     launcher.app.close()
     return 0

@@ -81,6 +81,9 @@ class RslRlPpoAlgorithmCfg:
     # h12env.ppo extension: a recurrent policy's update in the sequence form on the h12learn_lstm_seq_* kernels
     # (None: H12_RNN_UPDATE_FUSED)
     fused_rnn_update: bool | None = None
+    # h12env.ppo extension: gradient clip and Adam step as two HIP launches, h12env.optim.FusedClipAdam
+    # (None: H12_OPTIMIZER_FUSED)
+    fused_optimizer: bool | None = None
 
 
 @dataclass

@@ -1,6 +1,6 @@
 /* h12learn.h: learner-side device entry points of libh12env.so (csrc/h12_learn.hip, csrc/h12_policy.hip,
  * csrc/h12_policy_train.hip, csrc/h12_policy_rnn.hip, csrc/h12_policy_rnn_train.hip, csrc/h12_rnd.hip,
- * csrc/h12_ppo_head.hip).
+ * csrc/h12_optim.hip, csrc/h12_ppo_head.hip).
  *
  * The CleanRL PPO of the CaT tasks (h12env/cleanrl.py) calls two pieces of per-step / per-iteration work that
  * are launch-bound in torch: the running mean/variance normaliser and the soft-termination GAE.  The third piece,
@@ -355,6 +355,86 @@ typedef struct h12learn_rnd_finish_args {
 } h12learn_rnd_finish_args;
 
 int h12learn_rnd_finish(const h12learn_rnd_finish_args* args, void* stream);
+
+/* ---- fused optimiser step (csrc/h12_optim.hip; h12env/optim.py): the global gradient-norm clip
+ * of nn.utils.clip_grad_norm_ and the Adam or RAdam update of every parameter tensor, in two launches.
+ *
+ * Tensors.  n_tensors >= 1 contiguous fp32 tensors of numel[t] >= 1 elements, any 4-byte alignment: the parameter p[t],
+ * its gradient g[t] (read only: it is NOT rescaled in memory), the moments exp_avg[t] and exp_avg_sq[t], and step[t], a
+ * device fp32 scalar holding the number of steps taken so far, as torch's optimisers keep it.  p, g, exp_avg, exp_avg_sq,
+ * step and numel are HOST arrays of n_tensors entries; the device pointers travel in the kernels' arguments, so nothing
+ * is copied to the device and a captured step replays the addresses it saw.  No tensor may overlap another.
+ *
+ * Launch 1.  A block owns one chunk of h12learn_optim_chunk() elements of one tensor and writes the fp64 sum of g^2 over
+ * it (products and sums in fp64: a thread's elements in index order, a wave's lanes by an xor butterfly, the waves in
+ * order) to the workspace; one thread per tensor writes step[t] += 1.  It runs without a clip too.
+ * Launch 2.  Every block adds all partial sums in block-index order, h12learn_optim_fold() at a time through LDS, to S,
+ * and forms in double
+ *     norm = sqrt(S);   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1          (clip_grad_norm_'s)
+ *     s = step[t] (after launch 1);   lr = lr_dev ? *lr_dev : lr
+ *     bc1 = 1 - beta1^s;   bc2 = 1 - beta2^s
+ *     rho_inf = 2 / (1 - beta2) - 1;   rho_t = rho_inf - 2 s beta2^s / bc2
+ *     rect = sqrt((rho_t - 4) (rho_t - 2) rho_inf / ((rho_inf - 4) (rho_inf - 2) rho_t))
+ * Each of coef, 1 - beta1, beta2, 1 - beta2, eps, sqrt(bc2), -(lr / bc1), bc1, lr and rect is narrowed to fp32 once.  Then
+ * per element, in separately rounded fp32 operations (no contraction; sqrt and / correctly rounded), the expressions of
+ * torch 2.10's _single_tensor_adam / _single_tensor_radam in their non-capturable branches (Python-float scalars) with
+ * weight_decay = 0, no amsgrad, maximize = False:
+ *     g' = g * coef
+ *     m  = m + (g' - m) * (1 - beta1)                                     exp_avg.lerp_(grad, 1 - beta1)
+ *     v  = v * beta2;   v = v + (1 - beta2) * (g' * g')                   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, ..)
+ *   H12LEARN_OPTIM_ADAM
+ *     p  = p + (-(lr / bc1)) * (m / (sqrt(v) / sqrt(bc2) + eps))          param.addcdiv_(exp_avg, denom, value=-step_size)
+ *   H12LEARN_OPTIM_RADAM
+ *     u  = (m / bc1) * lr
+ *     rho_t > 5 (compared in double):  u = (u * ((1 / (sqrt(v) + eps)) * sqrt(bc2))) * rect
+ *     p  = p - u
+ * Block 0 writes (float)norm to grad_norm when it is not null.  rho_t comes from the step count in double: at
+ * beta2 = 0.999 it is 4.9960 at step 5 and 5.9942 at step 6, so rectification starts at step 6, as in torch's default
+ * (non-capturable) RAdam; an fp32 rho_t is off by 1 % of (rho_t - 4) there.
+ *
+ * Vector (16-byte) accesses where p, g, exp_avg and exp_avg_sq of a tensor are all 16-byte aligned, element accesses
+ * otherwise; which thread owns which element is the same on both paths, so every sum's order, and every output bit,
+ * depends on the tensor sizes alone.  More than h12learn_optim_max_tensors() tensors: further launches of each kernel
+ * (all of launch 1 first); the norm is over all tensors.  No atomics, nothing to initialise, every output bitwise
+ * reproducible.  Inputs are assumed finite. */
+#define H12LEARN_OPTIM_ADAM 0
+#define H12LEARN_OPTIM_RADAM 1
+
+typedef struct h12learn_optim_args {
+  int rule;      /* H12LEARN_OPTIM_* */
+  int n_tensors; /* >= 1 */
+  double beta1;  /* 0 <= beta < 1 */
+  double beta2;
+  double eps;      /* > 0 */
+  double max_norm; /* <= 0: no clip */
+  double lr;       /* >= 0; read when lr_dev is null */
+  const float* lr_dev; /* device scalar, or null */
+  float* const* p;           /* host arrays of n_tensors device pointers */
+  const float* const* g;
+  float* const* exp_avg;
+  float* const* exp_avg_sq;
+  float* const* step;        /* device fp32 scalars */
+  const long long* numel;    /* host array */
+  float* grad_norm; /* device scalar, or null */
+  void* workspace;  /* 8-byte aligned, h12learn_optim_workspace_bytes(numel, n_tensors) */
+  size_t workspace_bytes;
+} h12learn_optim_args;
+
+/* Elements of a block (the chunk C); a query so tests can place numel at C-1, C, C+1, 2C+1. */
+int h12learn_optim_chunk(void);
+
+/* Tensors one launch's table holds (K); K + 1 tensors take two launches of each kernel. */
+int h12learn_optim_max_tensors(void);
+
+/* Partial sums launch 2 stages at a time (F); F + 1 blocks take two rounds of its fold. */
+int h12learn_optim_fold(void);
+
+/* Bytes of workspace: one fp64 partial sum per block, sum_t ceil(numel[t] / C) of them.  0 with h12learn_last_error set
+ * when n_tensors or a numel is invalid. */
+size_t h12learn_optim_workspace_bytes(const long long* numel, int n_tensors);
+
+/* Two launches (norm, apply) for up to K tensors.  Every field is validated before any HIP call. */
+int h12learn_optim_step(const h12learn_optim_args* args, void* stream);
 
 /* ---- fused PPO loss head (csrc/h12_ppo_head.hip): everything PPO._minibatch (h12env/ppo.py) computes between the
  * networks' outputs and loss.backward(), in two launches: the minibatch gathers of the per-sample tensors, the Gaussian

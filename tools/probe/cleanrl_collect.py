@@ -5,6 +5,7 @@
     python tools/probe/cleanrl_collect.py --mode rocprof [--out FILE]
     python tools/probe/cleanrl_collect.py --mode head [--rounds 4] [--iters 6] [--out FILE]
     python tools/probe/cleanrl_collect.py --mode head_trace --arm default|fused_eager|fused_graphed [--out FILE]
+    python tools/probe/cleanrl_collect.py --mode head --arms fused_graphed,fused_graphed+optim [--out FILE]
 
 time (default): the two arms alternate in one process on one env (arm A fused, arm B torch, A, B, ...); each
 turn is one PPO() call of 1 + iters iterations whose first iteration (graph capture, allocator warm-up) is
@@ -20,7 +21,10 @@ every turn on its own, which is the spread between repeats of one arm.  Every lo
 arm is asserted finite.
 head_trace: one arm under `rocprofv3 --kernel-trace --stats` in a child process; the update's dispatches (from an
 iteration's GAE kernel to the next env step) per minibatch, split into GEMMs, ELU, optimiser and gradient clip (the
-multi-tensor kernels), the head's kernels and the rest.
+multi-tensor kernels and the capturable optimiser's scalar kernels on 0-dim tensors are in the rest), the head's
+kernels, the fused optimiser step's two kernels and the rest.
+The arms ``default+optim`` and ``fused_graphed+optim`` are ``default`` and ``fused_graphed`` with ``fused_optimizer`` on
+(h12env.optim.FusedClipRAdam); ``--arms`` picks the arms ``head`` alternates.
 """
 from __future__ import annotations
 
@@ -97,7 +101,10 @@ def mode_time(a):
     return out
 
 
-HEAD_ARMS = {"default": (False, "1"), "fused_eager": (True, "0"), "fused_graphed": (True, "1")}
+# arm -> (fused_loss, H12_PPO_GRAPH, fused_optimizer)
+HEAD_ARMS = {"default": (False, "1", False), "fused_eager": (True, "0", False), "fused_graphed": (True, "1", False),
+             "default+optim": (False, "1", True), "fused_graphed+optim": (True, "1", True)}
+HEAD_DEFAULT_ARMS = ("default", "fused_eager", "fused_graphed")
 
 
 def run_head_arm(env, arm: str, steps: int, iters: int, tmp: str):
@@ -107,14 +114,14 @@ def run_head_arm(env, arm: str, steps: int, iters: int, tmp: str):
     from biped_tasks.tasks.agents import H12_12dof_FlatCleanRlPPOCfg
     from h12env import cleanrl
 
-    fused_loss, graph = HEAD_ARMS[arm]
+    fused_loss, graph, fused_optimizer = HEAD_ARMS[arm]
     os.environ["H12_CLEANRL_FUSED"] = "1"
     os.environ["H12_PPO_GRAPH"] = graph
     cfg = H12_12dof_FlatCleanRlPPOCfg(num_steps=steps, num_iterations=1 + iters, save_interval=10 ** 9)
     cfg.minibatch_size = min(cfg.minibatch_size, steps * env.unwrapped.num_envs)
     run = tempfile.mkdtemp(dir=tmp)
     torch.manual_seed(1)
-    agent = cleanrl.PPO(env, cfg, run, fused_loss=fused_loss)
+    agent = cleanrl.PPO(env, cfg, run, fused_loss=fused_loss, fused_optimizer=fused_optimizer)
     torch.cuda.synchronize()
     all_lines = [json.loads(x) for x in open(os.path.join(run, "metrics.jsonl"))]
     for x in all_lines:
@@ -130,10 +137,11 @@ def run_head_arm(env, arm: str, steps: int, iters: int, tmp: str):
 
 def mode_head(a):
     env = make_env(a.num_envs)
-    res = {arm: ([], [], []) for arm in HEAD_ARMS}
+    arms = tuple(a.arms.split(",")) if a.arms else HEAD_DEFAULT_ARMS
+    res = {arm: ([], [], []) for arm in arms}
     with tempfile.TemporaryDirectory() as tmp:
         for _ in range(a.rounds):
-            for arm in HEAD_ARMS:
+            for arm in arms:
                 learn, whole, shape = run_head_arm(env, arm, a.steps, a.iters, tmp)
                 res[arm][0].extend(learn)
                 res[arm][1].extend(whole)
@@ -160,6 +168,8 @@ def _category(name: str) -> str:
     low = name.lower()
     if "cleanrl_" in low:
         return "head"
+    if "optim_norm_kernel" in low or "optim_apply_kernel" in low:
+        return "fused_optimiser"
     if "cijk" in low or "gemm" in low:
         return "gemm"
     if "elu" in low:
@@ -211,7 +221,8 @@ def mode_head_trace(a):
     for k, (calls, ns) in sorted(cats.items()):
         out["split"][k] = {"launches_per_minibatch": calls / n_mb, "gpu_us_per_minibatch": ns / n_mb / 1e3,
                            "share": ns / total}
-    top = sorted(names.items(), key=lambda kv: -kv[1][1])[:25]
+    by_time = sorted(names.items(), key=lambda kv: -kv[1][1])
+    top = by_time[:25] + [kv for kv in by_time[25:] if "optim_" in kv[0]]  # the fused optimiser's two, wherever they rank
     out["kernels"] = {k: {"calls_per_minibatch": c / n_mb, "avg_us": ns / c / 1e3} for k, (c, ns) in top}
     return out
 
@@ -249,6 +260,8 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("time", "short", "rocprof", "head", "head_short", "head_trace"), default="time")
     ap.add_argument("--arm", choices=tuple(HEAD_ARMS), default="default")
+    ap.add_argument("--arms", default=None, help="head: comma-separated arms to alternate (default: the three without "
+                                                "+optim)")
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=4)
